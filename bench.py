@@ -8,12 +8,14 @@ CTU every candidate TEncCu::xCompressCU tests -- merge / skip, SS + GT search fo
 CU sizes, the SS reference growing from the sentinel CU by CU, the coder contexts carried from CU to CU.  The candidates are evaluated by the HIP kernels of libhophip, the
 decisions taken by the host spine (hevc-hop_amd/host/hop_spine.cpp); the CTU rows run as a lag-8 wavefront (at most 16 rows in flight) whose requests are served in batches.
 The whole picture takes minutes, so it is coded CONTINUOUSLY on a thread of its own and a STEP is a fixed quantum of retired CTUs (one CTU row = 121) read from
-hop_encode_progress: the wavefront's ramp and `--warmup` steps are untimed, `--steps` steps are timed, then the run is cancelled (hop_encode_cancel).  A wall-clock budget
-(--budget-s, from process start) ends the timed region early if need be; the JSON says how many steps were timed.  `parity` in the JSON compares the RD costs of the CTUs
-this very run retired with cost.csv of the unmodified reference encoder for the same picture (tests/golden/encoder_frame_mi15_rows*.npz, oracle/make_golden24.py).
-`cpu_baseline` is that reference encoder (oracle/_ref/TAppEncoderRef) timed on a crop of the same frame; `roofline` / `kernels` come from a separate profiled pass with HIP
-events around every launch.  If time is left, BASELINE's config 5 (169 sub-aperture views of 624x432 as independent pictures in one stacked context) is measured as a second,
-separately named figure (`cfg5_views`).
+hop_encode_progress: untimed are the wavefront's ramp and `--warmup` steps (the ramp's CTUs count towards them), exactly `--steps` steps are timed, then the run is cancelled (hop_encode_cancel).
+`--dump-outputs DIR` writes what the last timed step computed (dump_outputs).  A plain run does nothing else.
+
+--full adds the passes beside the headline figure.  A wall-clock budget (--budget-s, from process start, 430 s with --full) ends the timed region early if need be; the
+JSON says how many steps were timed.  `parity` in the JSON compares the RD costs of the CTUs this very run retired with cost.csv of the unmodified reference encoder for the
+same picture (tests/golden/encoder_frame_mi15_rows*.npz, oracle/make_golden24.py).  `cpu_baseline` is that reference encoder (oracle/_ref/TAppEncoderRef) timed on a crop
+of the same frame; `roofline` / `kernels` come from a separate profiled pass with HIP events around every launch.  If time is left, BASELINE's config 5 (169 sub-aperture
+views of 624x432 as independent pictures in one stacked context) is measured as a second, separately named figure (`cfg5_views`).
 
 Multi-GPU: `bench.py --gpus N` spawns N ranks itself (torch.distributed.run; or the driver does).  Default: every rank codes its own frame of the sequence (no data-path
 collective, "scaling": "weak").  --shard-rows: ONE picture over all ranks -- the CTU rows dealt round-robin, every wavefront step's finished CTUs handed over by an all-gather
@@ -521,10 +523,49 @@ class EncodeRun:
 
 
 def frame_planes(fw, fh, seed):
-    """bench.py's frame: tests/hoputil.py:lenslet in numpy float64 on the host -- the SAME function oracle/make_golden24.py feeds the reference encoder with, so that
-    the per-CTU RD costs of a run can be compared with the reference's cost.csv (the GPU generator of --kernels mode is not reproducible on a CPU)"""
-    from hoputil import lenslet
-    return lenslet(fw, fh, PITCH, seed)
+    """bench.py's frame: tests/hoputil.py:lenslet(fw, fh, PITCH, seed) bit for bit -- the SAME planes oracle/make_golden24.py feeds the reference encoder with, so that
+    the per-CTU RD costs of a run can be compared with the reference's cost.csv (the GPU generator of --kernels mode is not reproducible on a CPU).  The random numbers are
+    drawn in lenslet's order; the element-wise float64 arithmetic runs in bands of rows on a few threads (numpy releases the GIL), which gives the same samples in a
+    fraction of the time (tests/test_multi_rank.py checks the equality)."""
+    from concurrent.futures import ThreadPoolExecutor
+    W, H, pitch, maxv, mid = fw, fh, PITCH, 255, 128
+    rng = np.random.default_rng(seed)
+
+    def tex_params():
+        out = []
+        for _ in range(4):
+            f = rng.uniform(0.02, 0.35, 2)
+            ph = rng.uniform(0, 2 * np.pi, 2)
+            out.append((f, ph, rng.uniform(0.4, 1.0)))
+        return out
+    py = tex_params()
+    noise = rng.normal(0, 2.0, (H, W))
+    pb, pr = tex_params(), tex_params()
+
+    def tex(ax, ay, prm):
+        t = np.zeros_like(ax)
+        for f, ph, a in prm:
+            t += a * np.sin(ax * f[0] + ph[0]) * np.cos(ay * f[1] + ph[1])
+        return t / 4.0
+    Y = np.empty((H, W), np.int16)
+    Cb, Cr = np.empty(((H + 1) // 2, (W + 1) // 2), np.int16), np.empty(((H + 1) // 2, (W + 1) // 2), np.int16)
+
+    def band(y0, y1):                                                      # y0 even: the chroma rows y0 / 2 ... of the band are its even luma rows
+        yy, xx = np.mgrid[y0:y1, 0:W].astype(np.float64)
+        mx, my = np.floor(xx / pitch), np.floor(yy / pitch)
+        ux, uy = xx - mx * pitch - pitch / 2.0, yy - my * pitch - pitch / 2.0
+        disp = 0.35
+        sx, sy = mx * pitch * 0.12 + ux * disp * 3.0, my * pitch * 0.12 + uy * disp * 3.0
+        vign = np.exp(-(ux ** 2 + uy ** 2) / (2 * (0.55 * pitch) ** 2))
+        y = (0.5 + 0.45 * tex(sx, sy, py)) * vign * maxv + noise[y0:y1]
+        Y[y0:y1] = np.clip(np.rint(y), 0, maxv).astype(np.int16)
+        cxx, cyy, cv, c0 = sx[::2, ::2], sy[::2, ::2], vign[::2, ::2], y0 // 2
+        Cb[c0:c0 + len(cxx)] = np.clip(np.rint(mid + 0.25 * maxv * tex(cxx, cyy, pb) * cv), 0, maxv).astype(np.int16)
+        Cr[c0:c0 + len(cxx)] = np.clip(np.rint(mid + 0.25 * maxv * tex(cxx, cyy, pr) * cv), 0, maxv).astype(np.int16)
+    rows = 64
+    with ThreadPoolExecutor(max_workers=min(16, len(os.sched_getaffinity(0)))) as ex:
+        list(ex.map(lambda y0: band(y0, min(H, y0 + rows)), range(0, H, rows)))
+    return Y, Cb, Cr
 
 
 def golden_costs(fh, Y, Cb, Cr):
@@ -659,12 +700,33 @@ def views_pass(hp, local, rank, world, slots, lag, budget_s, n_views=169, W=624,
             "rendezvous_rounds": st["rendezvous"]["rounds"]}
 
 
+def dump_outputs(out_dir, cost, bits, dist, parts, cols, rows, lag, retired, q):
+    """--dump-outputs DIR: what hop_encode_frame returns (per-CTU RD cost, bits, distortion and the CU partition records) for the CTUs of the last timed step, one
+    DIR/<name>.npy per array in float64 / float32, about 4 MB.  All CTUs of wavefront step s (CTU (r, c) belongs to step c + lag * r) start once step s - 1 is complete,
+    so which CTUs have retired when the count reaches a mark varies from run to run only inside one wavefront step.  The last step is therefore taken as the whole
+    wavefront steps that fit between the last step's nominal start and end counts (`retired` - `q`, `retired`): the same CTUs in every run with the same arguments."""
+    r, c = np.divmod(np.arange(rows * cols), cols)
+    step = c + lag * r
+    cum = np.cumsum(np.bincount(step))
+    s0, s1 = (int(np.searchsorted(cum, n, side="right")) - 1 for n in (retired - q, retired))    # the last wavefront step complete at n retired CTUs
+    sel = np.nonzero((step > s0) & (step <= s1))[0]
+    if len(sel) == 0 or not np.all(cost[sel] > 0):
+        raise SystemExit("bench.py --dump-outputs: the CTUs of the last step were not all retired")
+    arrays = {"ctu_index": sel.astype(np.float64), "cost": cost[sel].astype(np.float64), "bits": bits[sel].astype(np.float64), "dist": dist[sel].astype(np.float64)}
+    p = parts[sel]
+    for name in p.dtype.names:
+        arrays["part_" + name] = p[name].astype(np.float32)                  # (CTUs, 256 partition units[, k]): small integers, exact in float32
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def encode_main(args):
     """The default: BASELINE.json's metric on BASELINE's configuration -- the 7728 x 5368 lenslet frame coded as ONE picture, exactly as TEncSlice::compressSlice codes it with
     cfg/3DHencoder_intra_main.cfg --MIsize=15 and WaveFrontSynchro (one substream per CTU row): every candidate of TEncCu::xCompressCU for every CTU, the SS reference starting at
     the sentinel and growing CU by CU, coder contexts carried from CU to CU, the CTU rows as a wavefront of lag --lag.  The picture takes minutes, so it is coded CONTINUOUSLY (one
     hop_encode_frame on a thread of its own) and a STEP is a fixed quantum of retired CTUs (--step-ctus, default one CTU row = 121) read from hop_encode_progress: untimed are
-    the ramp (until the wavefront holds its maximum of rows) and `--warmup` steps; then `--steps` steps are timed; then the run is cancelled.  A wall-clock budget (--budget-s,
+    the ramp (until the wavefront holds its maximum of rows) and `--warmup` steps, the ramp counting towards them; then `--steps` steps are timed; then the run is cancelled.  A wall-clock budget (--budget-s,
     measured from process start) ends the timed region early if need be: `steps` in the JSON is what was timed.  With --gpus N every rank codes its own frame of the sequence."""
     t_proc = time.perf_counter() - (time.time() - PROC_T0)
     import threading
@@ -673,7 +735,7 @@ def encode_main(args):
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if args.gpus != world:
         raise SystemExit("bench.py --gpus %d but WORLD_SIZE is %d" % (args.gpus, world))
-    deadline = t_proc + args.budget_s
+    deadline = t_proc + args.budget_s if args.budget_s is not None else float("inf")
     fw, fh = args.width, min(args.height, args.rows * 64)
     shard = args.shard_rows and world > 1                                    # ONE picture over all ranks (its CTU rows dealt round-robin) instead of a picture per rank
     Y, Cb, Cr = frame_planes(fw, args.height, 2 + (0 if shard else rank))    # frame `rank` of the synthetic sequence: the same lenslet geometry, another texture seed
@@ -698,14 +760,18 @@ def encode_main(args):
     Q = args.step_ctus if args.step_ctus > 0 else cols
     if shard:                                                                # hop_encode_progress counts the CTUs THIS rank retired: its share of a step, of the ramp
         Q = max(1, Q // world); ramp_ctus = max(1, ramp_ctus // world)
+    warm_ctus = max(ramp_ctus, args.warmup * Q)                              # untimed: the ramp, which counts towards the warm-up steps
+    if warm_ctus + args.steps * Q > (n_ctu // world if shard else n_ctu):
+        raise SystemExit("bench.py: the %dx%d picture holds %d CTUs: after the warm-up (%d CTUs, the wavefront's ramp included) it has room for at most %d timed steps of "
+                         "%d CTUs, not %d" % (fw, fh, n_ctu, warm_ctus, ((n_ctu // world if shard else n_ctu) - warm_ctus) // Q, Q, args.steps))
 
     def barrier():
         torch.cuda.synchronize()
         if world > 1: dist.barrier()
 
-    # ---- rank 0, before the timed run and bounded: the CPU baseline and the profiled pass behind the roofline object ----
+    # ---- --full, rank 0, before the timed run and bounded: the CPU baseline and the profiled pass behind the roofline object ----
     extras = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             cb = cpu_baseline_reference(Y, Cb, Cr, args.cpu_crop[0], args.cpu_crop[1], args.cpu_budget_s) if not args.no_cpu else {"skipped": True}
             if cb is None: cb = cpu_baseline_port(Y, Cb, Cr, 6)
@@ -732,7 +798,7 @@ def encode_main(args):
     run = EncodeRun(ctx, lag, PITCH)
     ramp_deadline = min(deadline, time.perf_counter() + args.ramp_frac * max(1.0, deadline - time.perf_counter()))
     t_r, n_r = run.wait_progress(min(ramp_ctus, n_ctu), ramp_deadline)          # ramp: the wavefront fills
-    t_w, n_w = run.wait_progress(min(n_r + args.warmup * Q, n_ctu), deadline)   # warm-up steps
+    t_w, n_w = run.wait_progress(min(max(n_r, warm_ctus), n_ctu), deadline)   # the rest of the warm-up steps
     if world > 1: dist.barrier()                                                # all ranks enter the timed region together (their pictures keep running meanwhile)
     n0 = ctx.encode_progress(); t0 = time.perf_counter()
     marks = [(t0, n0)]
@@ -751,6 +817,10 @@ def encode_main(args):
     t1, n1 = marks[steps_done] if steps_done >= 1 else marks[-1]
     dt, ctus_timed = t1 - t0, n1 - n0
     cost, bits, dist_, parts, ncand = run.finish()
+    if steps_done != args.steps and args.budget_s is None:
+        raise SystemExit("bench.py: %d of %d timed steps completed (the picture ended early)" % (steps_done, args.steps))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, cost, bits, dist_, parts, cols, rows, lag, warm_ctus + steps_done * Q, Q)
     ctx.sync(); barrier()
     stats = ctx.encode_stats()
     retired = int(ctx.encode_progress())
@@ -765,8 +835,8 @@ def encode_main(args):
         ctus_all = ctus_timed
     if rank == 0:
         value = ctus_all / dt if dt > 0 else 0.0
-        # ---- parity of what was measured: the retired CTUs' RD costs against the reference encoder's cost.csv for the same frame ----
-        gold, meta, m = golden_costs(fh, Y, Cb, Cr)
+        # ---- --full: parity of what was measured, the retired CTUs' RD costs against the reference encoder's cost.csv for the same frame ----
+        gold, meta, m = golden_costs(fh, Y, Cb, Cr) if args.full else (None, "--full only", 0)
         done = cost > 0
         if gold is not None:
             sel = done[:m]
@@ -831,14 +901,14 @@ def encode_main(args):
             "candidates": ncand, "cost_sum_retired": float(cost[done].sum()),
             "cpu_baseline": extras.get("cpu_baseline"),
         }
+        if not args.full:                                                    # what the extra passes of --full measure
+            for k in ("parity", "roofline", "kernels", "cpu_baseline"):
+                del out[k]
     ctx.close()
     if gather is not None: gather.close()
-    if rank == 0:
-        try: open(os.path.join(ROOT, "gpurun_out", "bench_last.json"), "w").write(json.dumps(out))      # (kept in case the optional pass below is cut short)
-        except Exception: pass
-    # ---- the second workload (BASELINE config 5), when the wall-clock budget still has room for it: all ranks, each with its share of the views ----
+    # ---- --full: the second workload (BASELINE config 5), when the wall-clock budget still has room for it: all ranks, each with its share of the views ----
     t_left = t_proc + args.total_s - time.perf_counter()
-    want_views = args.views > 0 and t_left > args.views_min_s and not shard
+    want_views = args.full and args.views > 0 and t_left > args.views_min_s and not shard
     if world > 1:
         wv = torch.tensor([1 if want_views else 0], dtype=torch.int64, device="cpu" if shared else dev)
         dist.all_reduce(wv, op=dist.ReduceOp.MIN)
@@ -853,8 +923,8 @@ def encode_main(args):
             dist.all_reduce(vr, op=dist.ReduceOp.SUM)
             vp["ctu_per_s_all_gpus"] = float(vr.item())
         if rank == 0: out["cfg5_views"] = vp
-    elif rank == 0:
-        out["cfg5_views"] = {"skipped": "no room left in the wall-clock budget (%.0f s left); `bench.py --views 169 --steps 1 --warmup 0` measures it alone" % t_left}
+    elif rank == 0 and args.full:
+        out["cfg5_views"] = {"skipped": "no room left in the wall-clock budget (%.0f s left); `bench.py --full --views 169 --steps 1 --warmup 0` measures it alone" % t_left}
     if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
@@ -882,7 +952,8 @@ def main():
     ap.add_argument("--height", type=int, default=FRAME_H)
     ap.add_argument("--rows", type=int, default=84, help="CTU rows of the picture: 84 = the whole 7728x5368 frame; fewer = its full-width top band as one picture")
     ap.add_argument("--step-ctus", type=int, default=0, help="retired CTUs that make one step (0: one CTU row of the picture)")
-    ap.add_argument("--budget-s", type=float, default=430.0, help="wall-clock budget from process start: the timed region ends there at the latest (the driver's limit is 600 s)")
+    ap.add_argument("--budget-s", type=float, default=None, help="wall-clock budget from process start: the timed region ends there at the latest and the JSON says how many "
+                                                                  "steps were timed (default: none, every one of --steps is timed; 430 with --full)")
     ap.add_argument("--ramp-frac", type=float, default=0.55, help="at most this share of the time left when the picture starts goes into the ramp")
     ap.add_argument("--slots", type=int, default=48, help="candidate slots per context (the SS/GT candidates of a CU side by side); 0 = one after the other")
     ap.add_argument("--lag", type=int, default=8, help="wavefront lag in CTUs: row r codes CTU c once row r - 1 has finished CTU c + lag - 1.  8: identical to the reference on the whole frame (10 157 CTUs compared, --steps 76); 5 is faster (76 against 53 CTU/s) and leaves the reference at CTU 3079 (DESIGN.md section 5)")
@@ -898,7 +969,14 @@ def main():
     ap.add_argument("--cpu-ctus", type=int, default=None, help="--kernels: CTUs of the bounded cpu_baseline sample")
     ap.add_argument("--kernels", action="store_true", help="kernel-throughput mode of round 1: the search kernels over a frozen, fully reconstructed SS reference (not the encode metric)")
     ap.add_argument("--rqt", action="store_true", help="--kernels: run the whole residual-quadtree search of every 2Nx2N CU instead of its leaf step")
+    ap.add_argument("--full", action="store_true", help="also the passes beside the headline figure: the CPU baseline, the profiled pass (roofline, kernels), parity with "
+                                                        "the reference encoder's cost.csv and BASELINE config 5 (cfg5_views)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path computed in its last step as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.full and args.budget_s is None:
+        args.budget_s = 430.0
+    if args.dump_outputs and (args.kernels or args.shard_rows):
+        ap.error("--dump-outputs applies to the encode of a picture per GPU (not --kernels, not --shard-rows)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(sys.argv[1:], args.gpus)
     if args.kernels:

@@ -179,6 +179,36 @@ def test_bench_step_arithmetic_and_view_split():
     assert not np.array_equal(Y, Y2)                                # neighbouring views differ (disparity + their own noise)
 
 
+def test_bench_frame_is_the_lenslet_and_its_dump_the_last_wavefront_steps():
+    """bench.py's frame generator (row bands on threads) gives hoputil.lenslet's planes bit for bit -- the input of the goldens -- on pictures of several bands, odd
+    sizes included; --dump-outputs picks the same CTUs whichever CTUs of the step in flight have retired"""
+    import bench
+    from hoputil import lenslet
+    for W, H, seed in ((7728, 256, 2), (450, 202, 5), (131, 67, 3)):
+        for a, b in zip(bench.frame_planes(W, H, seed), lenslet(W, H, bench.PITCH, seed)):
+            assert a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b), (W, H)
+    import tempfile
+    sys.path.insert(0, os.path.join(ROOT, "hevc-hop_amd"))
+    import hophip
+    cols, rows, lag, Q = 121, 84, 8, 121
+    ramp, _ = bench.wavefront_ramp_ctus(cols, rows, lag)
+    r, c = np.divmod(np.arange(cols * rows), cols)
+    step = c + lag * r
+    rng = np.random.default_rng(1)
+    T = ramp + 3 * Q
+    got = []
+    for extra in (0, 7, 13):                                         # retired beyond the nominal count: part of the wavefront step in flight, in any order
+        order = np.lexsort((rng.random(len(step)), step))
+        cost = np.zeros(len(step)); cost[order[:T + extra]] = 1.0
+        with tempfile.TemporaryDirectory() as td:
+            bench.dump_outputs(td, cost, np.ones(len(step), np.uint32), np.ones(len(step), np.uint32), np.zeros((len(step), 256), hophip.CU_PART_DTYPE), cols, rows, lag, T, Q)
+            got.append(np.load(os.path.join(td, "ctu_index.npy")))
+            assert np.load(os.path.join(td, "part_mv.npy")).shape == (len(got[-1]), 256, 2)
+    assert len(got[0]) > 0 and all(np.array_equal(got[0], g) for g in got)
+    sel = got[0].astype(int)
+    assert step[sel].min() > step[order[T - Q - 1]] - 1 and step[sel].max() <= step[order[T - 1]]
+
+
 def _shard_worker(rank, world, port, W, H, seed, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
