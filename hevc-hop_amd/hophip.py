@@ -117,6 +117,10 @@ class DeblockParams(ctypes.Structure):   # hop_deblock_params
                 ("disable", ctypes.c_int32)]
 
 
+class DecParams(ctypes.Structure):       # hop_dec_params
+    _fields_ = [("qp", ctypes.c_int32), ("cb_qp_offset", ctypes.c_int32), ("cr_qp_offset", ctypes.c_int32), ("plain_intra", ctypes.c_int32), ("schedule", ctypes.c_int32)]
+
+
 _I16P = ctypes.POINTER(ctypes.c_int16)
 
 
@@ -130,7 +134,7 @@ MIRRORS = {"hop_pu_job": PU_JOB_DTYPE, "hop_pu_result": PU_RESULT_DTYPE, "hop_pr
            "hop_tu_rd_result": TU_RD_RESULT_DTYPE, "hop_intra_modes_job": INTRA_MODES_JOB_DTYPE, "hop_intra_modes_result": INTRA_MODES_RESULT_DTYPE, "hop_rqt_job": RQT_JOB_DTYPE,
            "hop_rqt_result": RQT_RESULT_DTYPE, "hop_cu_syntax": CU_SYNTAX_DTYPE, "hop_intra_cu_syntax": INTRA_CU_SYNTAX_DTYPE, "hop_intra_rqt_opt": INTRA_RQT_OPT_DTYPE,
            "hop_intra_search_job": INTRA_SEARCH_JOB_DTYPE, "hop_intra_search_result": INTRA_SEARCH_RESULT_DTYPE, "hop_cu_part": CU_PART_DTYPE, "hop_enc_params": EncParams,
-           "hop_deblock_params": DeblockParams, "hop_sao_param": SAO_PARAM_DTYPE, "hop_sao_params": SaoParams}
+           "hop_deblock_params": DeblockParams, "hop_sao_param": SAO_PARAM_DTYPE, "hop_sao_params": SaoParams, "hop_dec_params": DecParams}
 
 
 def mirror_size(m):
@@ -224,7 +228,7 @@ class Context:
         if pictures > 1:
             self.pitch = self.L.hop_stack_pitch(pic_h)
             pic_h = (pictures - 1) * self.pitch + pic_h
-        self.W, self.H = pic_w, pic_h
+        self.W, self.H, self.bit_depth = pic_w, pic_h, bit_depth
         r = self.L.hop_ctx_create(ctypes.byref(self.h), pic_w, pic_h, bit_depth, bit_depth, device)
         if r != 0:
             raise HopError("hop_ctx_create: %d %s" % (r, self.L.hop_last_error(None).decode()))
@@ -396,6 +400,21 @@ class Context:
         assert recon.nbytes == self._n_ctu() * 3 * SAO_PARAM_DTYPE.itemsize
         self.L.hop_sao_apply.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         self._chk(self.L.hop_sao_apply(self.h, recon.ctypes.data), "hop_sao_apply")
+
+    def decode_frame(self, parts, levels, qp=32, cb_qp_offset=0, cr_qp_offset=0, plain_intra=0, schedule=0):
+        """hop_decode_frame: the picture reconstructed from parts (n_ctu, 256) CU_PART_DTYPE and levels (n_ctu, 6144) int32 as encode_frame / levels_download give
+        them; afterwards recon_download / ssref_download / deblock_frame / sao_apply work as after an encode.  schedule 0: dependency levels, 1: raster."""
+        parts = np.ascontiguousarray(parts, CU_PART_DTYPE); levels = np.ascontiguousarray(levels, np.int32)
+        n = self._n_ctu()
+        if parts.size != n * 256 or levels.size != n * 6144:
+            raise HopError("decode_frame: %d CTUs need (%d, 256) parts and (%d, 6144) levels" % (n, n, n))
+        p = DecParams(qp, cb_qp_offset, cr_qp_offset, plain_intra, schedule)
+        self.L.hop_decode_frame.argtypes = [ctypes.c_void_p] * 4
+        self._chk(self.L.hop_decode_frame(self.h, ctypes.byref(p), parts.ctypes.data, levels.ctypes.data), "hop_decode_frame")
+
+    def sao_reconstruct_params(self, coded, bit_depth=None):
+        """hop_sao_reconstruct_params for this context's picture: coded (n_ctu, 3) SAO_PARAM_DTYPE -> what sao_apply takes"""
+        return sao_reconstruct_params(coded, (self.W + 63) // 64, bit_depth or self.bit_depth)
 
     def psnr(self):
         """hop_psnr: (ssd (pictures, 3) uint64, psnr (pictures, 3) float64) between the resident original and the reconstruction"""
@@ -575,3 +594,41 @@ class Context:
 
     def sync(self):
         self._chk(self.L.hop_sync(self.h), "hop_sync")
+
+
+def decode_schedule(W, H, parts, schedule=0, lib=None):
+    """hop_decode_schedule: (level of every CTU (n_ctu,) int32, number of levels) -- the launches hop_decode_frame makes; HopError for refused parts"""
+    L = lib or load()
+    parts = np.ascontiguousarray(parts, CU_PART_DTYPE)
+    n = ((W + 63) // 64) * ((H + 63) // 64)
+    if parts.size != n * 256:
+        raise HopError("decode_schedule: %d CTUs need (%d, 256) parts" % (n, n))
+    lv = np.zeros(n, np.int32); nl = ctypes.c_int32(0)
+    L.hop_decode_schedule.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    r = L.hop_decode_schedule(W, H, parts.ctypes.data, schedule, lv.ctypes.data, ctypes.byref(nl))
+    if r != 0:
+        raise HopError("hop_decode_schedule: %d" % r)
+    return lv, int(nl.value)
+
+
+def decode_footprint(W, H, job, lib=None):
+    """hop_decode_footprint: the CTUs (ascending raster addresses) whose samples the predictor of one PU (a PredJob) reads"""
+    L = lib or load()
+    L.hop_decode_footprint.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+    out = np.zeros(((W + 63) // 64) * ((H + 63) // 64), np.int32)
+    r = L.hop_decode_footprint(W, H, ctypes.byref(job), out.ctypes.data, out.size)
+    if r < 0:
+        raise HopError("hop_decode_footprint: %d" % r)
+    return out[:r]
+
+
+def sao_reconstruct_params(coded, ctus_per_row, bit_depth, lib=None):
+    """hop_sao_reconstruct_params: coded SAO parameters (n_ctu, 3) SAO_PARAM_DTYPE -> the reconstructed ones hop_sao_apply takes"""
+    L = lib or load()
+    coded = np.ascontiguousarray(coded, SAO_PARAM_DTYPE)
+    recon = np.zeros_like(coded)
+    L.hop_sao_reconstruct_params.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    r = L.hop_sao_reconstruct_params(coded.size // 3, ctus_per_row, bit_depth, coded.ctypes.data, recon.ctypes.data)
+    if r != 0:
+        raise HopError("hop_sao_reconstruct_params: %d" % r)
+    return recon

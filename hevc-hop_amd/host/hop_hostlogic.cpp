@@ -286,6 +286,7 @@ int hop_sizeof(const char* name) {
   S(hop_deblock_params);
   S(hop_sao_param);
   S(hop_sao_params);
+  S(hop_dec_params);
 #undef S
   return -1;
 }

@@ -137,6 +137,15 @@ void set_param(hop_sao_param& p, int mode, int type, int aux, const int* off) {
   if (off) for (int i = 0; i < 32; i++) p.offset[i] = (int8_t)off[i];
 }
 
+// reconstructBlkSAOParam (TComSampleAdaptiveOffset.cpp:305-339): merges resolved to the candidate's reconstructed parameters, new offsets scaled
+void reconstruct_blk(const Ctx& c, const hop_sao_param* coded, const hop_sao_param* const merge[2], hop_sao_param* recon) {
+  for (int comp = 0; comp < 3; comp++) {
+    hop_sao_param& r = recon[comp]; r = coded[comp];
+    if (r.mode == SAO_NEW) { int src[32], dst[32]; for (int i = 0; i < 32; i++) src[i] = r.offset[i]; invert_quant(c, r.type, r.aux, dst, src); for (int i = 0; i < 32; i++) r.offset[i] = (int8_t)dst[i]; }
+    else if (r.mode == SAO_MERGE) r = merge[r.type][comp];
+  }
+}
+
 // coder labels of the reference: CUR = the CTU's entry state, MID / TEMP inside a mode, NEXT = the winner's exit state
 void mode_new(const Ctx& c, int ctu, const hop_sao_param* merge[2], hop_sao_param out[3], double& norm_cost, Coder& goon, const Coder& cur, Coder& temp) {   // deriveModeNewRDO :565-704
   int64_t dist[3], mode_dist[3] = { 0, 0, 0 };
@@ -230,12 +239,27 @@ extern "C" int hop_sao_decide(int n_ctu, int ctus_per_row, int bit_depth, const 
     mode_merge(c, ctu, merge, mode, cost, goon, cur, temp);
     if (cost < min_cost) { min_cost = cost; memcpy(&coded[(size_t)ctu * 3], mode, sizeof(mode)); next = goon; }
     goon = next;
-    // reconstructBlkSAOParam (TComSampleAdaptiveOffset.cpp:305-339)
+    reconstruct_blk(c, coded + (size_t)ctu * 3, merge, recon + (size_t)ctu * 3);
+  }
+  return HOP_OK;
+}
+
+extern "C" int hop_sao_reconstruct_params(int n_ctu, int ctus_per_row, int bit_depth, const hop_sao_param* coded, hop_sao_param* recon) {
+  if (n_ctu <= 0 || ctus_per_row <= 0 || !coded || !recon || bit_depth < 8 || bit_depth > 12) return HOP_ERR_ARG;
+  Ctx c; memset(&c, 0, sizeof(c));
+  c.bit_depth = bit_depth; c.step_log2 = bit_depth > 10 ? bit_depth - 10 : 0;
+  for (int ctu = 0; ctu < n_ctu; ctu++) {                               // the whole input first: nothing is written for a malformed one
+    const bool has[2] = { ctu % ctus_per_row != 0, ctu >= ctus_per_row };
     for (int comp = 0; comp < 3; comp++) {
-      hop_sao_param& r = recon[(size_t)ctu * 3 + comp]; r = coded[(size_t)ctu * 3 + comp];
-      if (r.mode == SAO_NEW) { int src[32], dst[32]; for (int i = 0; i < 32; i++) src[i] = r.offset[i]; invert_quant(c, r.type, r.aux, dst, src); for (int i = 0; i < 32; i++) r.offset[i] = (int8_t)dst[i]; }
-      else if (r.mode == SAO_MERGE) r = merge[r.type][comp];
+      const hop_sao_param& p = coded[(size_t)ctu * 3 + comp];
+      if (p.mode < SAO_OFF || p.mode > SAO_MERGE) return HOP_ERR_ARG;
+      if (p.mode == SAO_NEW && (p.type < 0 || p.type > TYPE_BO || p.aux < 0 || p.aux >= BO_CLASSES)) return HOP_ERR_ARG;
+      if (p.mode == SAO_MERGE && (p.type < 0 || p.type > 1 || !has[p.type])) return HOP_ERR_ARG;
     }
+  }
+  for (int ctu = 0; ctu < n_ctu; ctu++) {                               // in raster order: a merge takes its candidate's reconstructed parameters (getMergeList)
+    const hop_sao_param* merge[2] = { ctu % ctus_per_row ? &recon[(size_t)(ctu - 1) * 3] : NULL, ctu >= ctus_per_row ? &recon[(size_t)(ctu - ctus_per_row) * 3] : NULL };
+    reconstruct_blk(c, coded + (size_t)ctu * 3, merge, recon + (size_t)ctu * 3);
   }
   return HOP_OK;
 }

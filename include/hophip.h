@@ -732,6 +732,35 @@ int hop_sao_frame(hop_ctx* ctx, const hop_sao_params* params, hop_sao_param* cod
  * dB (99.99 for an exact picture).  Either output may be NULL. */
 int hop_psnr(hop_ctx* ctx, uint64_t* ssd, double* psnr);
 
+/* ---- the decoder side: a picture reconstructed on the device from its syntax ---- */
+/* replaces: the reconstruction half of TDecSlice::decompressSlice (TLibDecoder/TDecSlice.cpp) -- TDecCu::decompressCtu / xDecompressCU (TLibDecoder/TDecCu.cpp:383-476)
+ * with xReconIntraQT, xReconInter and the SS-reference commit xFindSSRef2Copy -- for one picture whose CUs have been parsed.  parts: 256 hop_cu_part per CTU in z-order,
+ * levels: 6144 per CTU, in exactly the layouts hop_encode_frame / hop_levels_download produce.  The SS reference is reset to the sentinel, then every CU is predicted
+ * (intra from the reconstruction picture, SS / GT from the SS reference), its residual dequantised and inverse-transformed and added, and the CU committed to the SS
+ * reference, in the reference decoder's order: CTUs in raster order, CUs in z-order.  Afterwards hop_recon_download, hop_deblock_frame, hop_sao_apply and
+ * hop_ssref_download work as after hop_encode_frame.  No original is needed.
+ * schedule 0: the CTUs run in levels of a dependency graph (hop_decode_schedule), one launch per level, every CTU seeing the SS-reference state raster order gives it;
+ * schedule 1: raster order, one CTU per launch (the yardstick).  Both give the same picture.  One picture per context: a stacked or sharded context is refused; so is
+ * malformed partition data (inconsistent CU fields, directions outside 0..34 / DM, transform depths out of range, a vector or GT footprint outside the padded plane
+ * and its guard rows, SS/GT CUs with plain_intra, the HOP configuration at a bit depth other than 8), before anything is enqueued.  Synchronous. */
+typedef struct {
+  int32_t qp, cb_qp_offset, cr_qp_offset;   /* slice QP and pps_cb_qp_offset / pps_cr_qp_offset */
+  int32_t plain_intra;                      /* as hop_enc_params.plain_intra: 1 an I slice at the context's bit depth, 0 the HOP configuration (SS / GT CUs, 8 bit) */
+  int32_t schedule;                         /* 0 dependency levels (default), 1 raster, one CTU per launch */
+} hop_dec_params;
+int hop_decode_frame(hop_ctx* ctx, const hop_dec_params* params, const hop_cu_part* parts, const int32_t* levels);
+/* host only: the checks of hop_decode_frame and the level each CTU is decoded in (ctu_level: one per CTU, raster order; n_levels: the number of launches).  The
+ * levels respect, for every CTU, its left, above-left, above and above-right neighbours and, for every SS / GT PU, the CTUs its prediction reads: a raster-earlier one
+ * in a lower level, a raster-later one in a higher level. */
+int hop_decode_schedule(int pic_w, int pic_h, const hop_cu_part* parts, int schedule, int32_t* ctu_level, int32_t* n_levels);
+/* host only: the CTUs (raster addresses, ascending) whose samples -- margin samples counted with the border sample they replicate -- the predictor of one PU
+ * (hop_pred_inter) reads, luma and chroma; returns their number (only the first max_ctus are written), HOP_ERR_ARG for a footprint outside the padded plane. */
+int hop_decode_footprint(int pic_w, int pic_h, const hop_pred_job* pu, int32_t* ctus, int max_ctus);
+/* host only: replaces TComSampleAdaptiveOffset::reconstructBlkSAOParam (TLibCommon/TComSampleAdaptiveOffset.cpp:305-339) with the merge-list lookup of getMergeList:
+ * the coded parameters of n_ctu CTUs (3 per CTU, as hop_sao_decide / hop_sao_frame return them) into what hop_sao_apply takes.  HOP_ERR_ARG for a merge without its
+ * candidate or a mode / type out of range. */
+int hop_sao_reconstruct_params(int n_ctu, int ctus_per_row, int bit_depth, const hop_sao_param* coded, hop_sao_param* recon);
+
 /* ---- profiling (bench.py roofline): HIP events around every kernel launch on the context stream ---- */
 #define HOP_K_SS_SEARCH 0
 #define HOP_K_FRAC      1
