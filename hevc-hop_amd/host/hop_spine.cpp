@@ -12,6 +12,7 @@
 #include "hop_spine.h"
 #include <map>
 #include <deque>
+#include <exception>
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -1196,11 +1197,13 @@ void Encoder::encode_frame(int first_ctus) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// wavefront: one thread per CTU row, requests of the rows in flight rendezvous and are served in batches
+// wavefront: the CTU rows in flight side by side (code_row), step by step (WavefrontSteps).  Two forms: the rows as fibers whose requests meet and are served in
+// batches (FiberPool), or one thread per row on backends of their own
 // ---------------------------------------------------------------------------------------------------------------------------------
 namespace {
-struct Req { int kind; int lane; int n; const void* a; const void* b; void* out; int i0, i1, i2, i3; bool done; uint64_t tag; std::condition_variable* wake; bool posted; int worker; };   // wake: the submitting thread's own (only it is woken when the request is done)
+struct Req { int kind; int n; const void* a; const void* b; void* out; int i0, i1, i2, i3; bool done; uint64_t tag; bool posted; int worker; };
 enum { RQ_ME, RQ_PRED, RQ_DIST, RQ_VALID, RQ_INTER, RQ_INTRA, RQ_SAVE, RQ_RESTORE, RQ_COMMIT, RQ_PCOST, RQ_NOP };   // RQ_NOP: nothing but the round (FiberPool::flush)
+static Req req(int kind, int n, const void* a, const void* b, void* out, int i0 = 0, int i1 = 0, int i2 = 0, int i3 = 0) { Req q = { kind, n, a, b, out, i0, i1, i2, i3, false, 0, false, 0 }; return q; }
 
 // one group of requests of the same kind (and class) as one call of the batching backend
 static void run_group(BatchInner* inner_, std::vector<Req*>& g) {
@@ -1248,81 +1251,10 @@ static void run_group(BatchInner* inner_, std::vector<Req*>& g) {
   }
 }
 
-class Rendezvous : public Backend {
- public:
-  Rendezvous(BatchInner* inner, int n_threads) : rounds(0), requests(0), inner_(inner), active_(n_threads), failed_(false) { memset(tag_of_, 0, sizeof(tag_of_)); }
-  void set_tag(int lane, uint64_t tag) { tag_of_[lane % SPINE_LANES] = tag; }
-  // a row thread is about to block on another row's progress / has been released / has finished
-  std::mutex m; std::condition_variable cv;
-  void begin_frame() {}
-  void me_search(int lane, int n, const hop_pu_job* j, hop_pu_result* r) { Req q = { RQ_ME, lane, n, j, NULL, r, 0, 0, 0, 0, false }; submit(q); }
-  void pred_inter(int lane, int n, const hop_pred_job* j) { Req q = { RQ_PRED, lane, n, j, NULL, NULL, 0, 0, 0, 0, false }; submit(q); }
-  void distortion(int lane, int n, const hop_dist_job* j, uint32_t* o) { Req q = { RQ_DIST, lane, n, j, NULL, o, 0, 0, 0, 0, false }; submit(q); }
-  void valid_pattern(int lane, int n, const int32_t* v, uint8_t* o) { Req q = { RQ_VALID, lane, n, v, NULL, o, 0, 0, 0, 0, false }; submit(q); }
-  void pred_cost(int lane, int n, const hop_pred_job* j, int kind, uint32_t* o) { Req q = { RQ_PCOST, lane, n, j, NULL, o, kind, 0, 0, 0, false }; submit(q); }
-  void inter_cu(int lane, const InterEval& e, const Coder& in, EvalResult& o) { Req q = { RQ_INTER, lane, 1, &e, &in, &o, e.job.log2_cu, e.skip_res, 0, 0, false }; submit(q); }
-  void intra_cu(int lane, const IntraEval& e, const Coder& in, EvalResult& o) { Req q = { RQ_INTRA, lane, 1, &e, &in, &o, e.job.log2_cu, e.part_nxn, 0, 0, false }; submit(q); }
-  void recon_save(int lane, int slot, int x, int y, int size) { Req q = { RQ_SAVE, lane, 1, NULL, NULL, NULL, x, y, size, lane * 16 + slot, false }; submit(q); }
-  void recon_restore(int lane, int slot, int x, int y, int size) { Req q = { RQ_RESTORE, lane, 1, NULL, NULL, NULL, x, y, size, lane * 16 + slot, false }; submit(q); }
-  void commit(int lane, int x, int y, int size) { Req q = { RQ_COMMIT, lane, 1, NULL, NULL, NULL, x, y, size, 0, false }; submit(q); }
-  void restore_commit(int lane, int slot, int x, int y, int size) { Req q = { RQ_COMMIT, lane, 1, NULL, NULL, NULL, x, y, size, lane * 16 + slot + 1, false }; submit(q); }
-  // progress waits of the row threads go through the same lock so that "nobody can run" is detected exactly
-  template <class Pred> void wait_until(std::unique_lock<std::mutex>& lk, Pred p) {
-    if (p()) return;
-    idle(lk);
-    cv.wait(lk, [&] { return p() || failed_; });
-    active_++;
-  }
-  void thread_done(std::unique_lock<std::mutex>& lk) { idle(lk); }
-  bool failed() const { return failed_; }
-  uint64_t rounds, requests;
- private:
-  BatchInner* inner_; int active_; bool failed_; std::vector<Req*> pending_; uint64_t tag_of_[SPINE_LANES];
-  void idle(std::unique_lock<std::mutex>& lk) {       // the caller stops running; if it was the last one, it serves what is pending first
-    active_--;
-    while (active_ == 0 && !pending_.empty()) serve(lk);
-  }
-  void submit(Req& q) {
-    std::unique_lock<std::mutex> lk(m);
-    if (failed_) throw 1;
-    q.tag = tag_of_[q.lane % SPINE_LANES];
-    std::condition_variable mine; q.wake = &mine;
-    pending_.push_back(&q);
-    active_--;
-    while (active_ == 0 && !pending_.empty() && !q.done) serve(lk);
-    mine.wait(lk, [&] { return q.done || failed_; });
-    if (failed_ && !q.done) { for (size_t i = 0; i < pending_.size(); i++) if (pending_[i] == &q) { pending_.erase(pending_.begin() + i); break; } throw 1; }
-  }
-  void serve(std::unique_lock<std::mutex>&) {         // called with the lock held and every thread parked: one batch per kind / class
-    // the requests with the smallest tag (the rows coded side by side have started their CTUs together: equal tags are the same operation); the others wait their turn
-    uint64_t tmin = ~0ull; for (Req* r : pending_) if (r->tag < tmin) tmin = r->tag;
-    std::vector<Req*> v, rest;
-    for (Req* r : pending_) (r->tag == tmin ? v : rest).push_back(r);
-    pending_.swap(rest);
-    rounds++; requests += v.size();
-    try {
-      std::vector<char> used(v.size(), 0);
-      for (size_t i = 0; i < v.size(); i++) {
-        if (used[i]) continue;
-        std::vector<Req*> g;
-        for (size_t k = i; k < v.size(); k++) {
-          if (used[k] || v[k]->kind != v[i]->kind) continue;
-          if ((v[i]->kind == RQ_INTER || v[i]->kind == RQ_INTRA) && (v[k]->i0 != v[i]->i0 || v[k]->i1 != v[i]->i1)) continue;
-          used[k] = 1; g.push_back(v[k]);
-        }
-        run_group(inner_, g);
-      }
-    } catch (...) { failed_ = true; }
-    for (size_t i = 0; i < v.size(); i++) { v[i]->done = true; v[i]->wake->notify_one(); }
-    active_ += (int)v.size();
-    if (failed_) { for (Req* r : pending_) r->wake->notify_one(); cv.notify_all(); }   // everybody gives up
-  }
-};
-
-// The same rendezvous without a thread per CTU row: the rows are FIBERS (ucontext) spread over a few worker threads.  A row that submits a request, or waits for the
-// wavefront to advance, switches back to its worker's scheduler; a worker whose rows are all waiting joins a barrier; when every worker is there the requests with the
-// smallest tag are served as one batch per kind (exactly as above) and the workers go round again.  A request costs two context switches in user space instead of a futex
-// sleep and wake-up per row thread -- with hundreds of rows in flight (several pictures side by side) those wake-ups were the largest single cost of the host side.
+// The rows are FIBERS spread over a few worker threads.  A row that submits a request, or waits for a counter another fiber moves (the wavefront's steps), switches
+// back to its worker's scheduler; a worker whose rows are all waiting joins a barrier; when every worker is there the requests with the smallest tag are served as one
+// batch per kind and class and the workers go round again.  A request costs two context switches in user space instead of a futex sleep and wake-up of a thread per row
+// -- with hundreds of rows in flight (several pictures side by side) those wake-ups were the largest single cost of the host side.
 // The context switch: callee-saved registers on the leaving stack, stack pointers exchanged.  (glibc's swapcontext also saves and restores the signal mask, two
 // system calls per switch: at four switches per request that was most of the rows' host time.)  x86-64 System V, like everything else here.
 extern "C" void hop_fiber_switch(void** save_sp, void* load_sp);
@@ -1334,15 +1266,15 @@ asm(".text\n.globl hop_fiber_switch\n.type hop_fiber_switch,@function\nhop_fiber
 
 class FiberPool : public Backend {
  public:
-  struct Fiber { void* sp; char* stack; std::function<void()> body; bool done; Req* req; int wait_step; int worker; FiberPool* pool;
+  struct Fiber { void* sp; char* stack; std::function<void()> body; bool done; Req* req; int worker; FiberPool* pool;
                  Fiber* parent; int live_children; bool wait_children; uint64_t tag;      // parent: a child of fork_join (recycled when done)
                  std::atomic<int>* wait_ctr; int wait_target; };                        // waiting until *wait_ctr >= wait_target
-  FiberPool(BatchInner* inner, int n_workers) : rounds(0), requests(0), steps_complete(-1), inner_(inner), T_(n_workers), failed_(false), finished_(false), arrived_(0), gen_(0), left_(0), idle_rounds_(0) {
+  FiberPool(BatchInner* inner, int n_workers) : rounds(0), requests(0), inner_(inner), T_(n_workers), failed_(false), finished_(false), arrived_(0), gen_(0), left_(0), idle_rounds_(0) {
     sched_.resize(T_); mine_.resize(T_); local_.resize(T_); free_.resize(T_); kids_.resize(T_); pstore_.resize(T_); pjobs_.resize(T_);
   }
   ~FiberPool() { for (Fiber* f : all_) { stack_free(f->stack); delete f; } for (auto& v : kids_) for (Fiber* f : v) { stack_free(f->stack); delete f; } }
   void add(std::function<void()> body) {
-    Fiber* f = new Fiber(); f->stack = stack_alloc(); f->body = body; f->done = false; f->req = NULL; f->wait_step = -1; f->worker = (int)(all_.size() % T_); f->pool = this;
+    Fiber* f = new Fiber(); f->stack = stack_alloc(); f->body = body; f->done = false; f->req = NULL; f->worker = (int)(all_.size() % T_); f->pool = this;
     f->parent = NULL; f->live_children = 0; f->wait_children = false; f->tag = 0; f->wait_ctr = NULL; f->wait_target = 0;
     all_.push_back(f); mine_[f->worker].push_back(f); left_++;
   }
@@ -1358,7 +1290,7 @@ class FiberPool : public Backend {
       if (!free_[w].empty()) { f = free_[w].back(); free_[w].pop_back(); }
       else { f = new Fiber(); f->stack = stack_alloc(); kids_[w].push_back(f); }
       f->body = [&fn, i]() { fn(i); };
-      f->done = false; f->req = NULL; f->wait_step = -1; f->worker = w; f->pool = this; f->parent = me; f->live_children = 0; f->wait_children = false; f->tag = me->tag;
+      f->done = false; f->req = NULL; f->worker = w; f->pool = this; f->parent = me; f->live_children = 0; f->wait_children = false; f->tag = me->tag;
       f->wait_ctr = NULL; f->wait_target = 0;
       start(f);
       mine_[w].push_back(f);
@@ -1376,21 +1308,21 @@ class FiberPool : public Backend {
   // ---- called from inside fibers ----
   void set_tag(int, uint64_t tag) { current()->tag = tag; }            // the tag belongs to the fiber (children of fork_join carry their own)
   void begin_frame() {}
-  void me_search(int lane, int n, const hop_pu_job* j, hop_pu_result* r) { Req q = { RQ_ME, lane, n, j, NULL, r, 0, 0, 0, 0, false, 0, NULL }; submit(q); }
-  void pred_inter(int lane, int n, const hop_pred_job* j) { Req q = { RQ_PRED, lane, n, j, NULL, NULL, 0, 0, 0, 0, false, 0, NULL }; if (posted_preds_) post(q, j); else submit(q); }
-  void distortion(int lane, int n, const hop_dist_job* j, uint32_t* o) { Req q = { RQ_DIST, lane, n, j, NULL, o, 0, 0, 0, 0, false, 0, NULL }; submit(q); }
-  void valid_pattern(int lane, int n, const int32_t* v, uint8_t* o) { Req q = { RQ_VALID, lane, n, v, NULL, o, 0, 0, 0, 0, false, 0, NULL }; submit(q); }
-  void pred_cost(int lane, int n, const hop_pred_job* j, int kind, uint32_t* o) { Req q = { RQ_PCOST, lane, n, j, NULL, o, kind, 0, 0, 0, false, 0, NULL }; submit(q); }
-  void inter_cu(int lane, const InterEval& e, const Coder& in, EvalResult& o) { Req q = { RQ_INTER, lane, 1, &e, &in, &o, e.job.log2_cu, e.skip_res, 0, 0, false, 0, NULL }; submit(q); }
-  void intra_cu(int lane, const IntraEval& e, const Coder& in, EvalResult& o) { Req q = { RQ_INTRA, lane, 1, &e, &in, &o, e.job.log2_cu, e.part_nxn, 0, 0, false, 0, NULL }; submit(q); }
-  void recon_save(int lane, int slot, int x, int y, int size) { Req q = { RQ_SAVE, lane, 1, NULL, NULL, NULL, x, y, size, lane * 16 + slot, false, 0, NULL }; if (posted_mode_ && (posted_kinds_ & 1)) post(q, NULL); else submit(q); }
-  void recon_restore(int lane, int slot, int x, int y, int size) { Req q = { RQ_RESTORE, lane, 1, NULL, NULL, NULL, x, y, size, lane * 16 + slot, false, 0, NULL }; if (posted_mode_ && (posted_kinds_ & 2)) post(q, NULL); else submit(q); }
-  void commit(int lane, int x, int y, int size) { Req q = { RQ_COMMIT, lane, 1, NULL, NULL, NULL, x, y, size, 0, false, 0, NULL }; if (posted_mode_ && (posted_kinds_ & 4)) post(q, NULL); else submit(q); }
+  void me_search(int, int n, const hop_pu_job* j, hop_pu_result* r) { Req q = req(RQ_ME, n, j, NULL, r); submit(q); }
+  void pred_inter(int, int n, const hop_pred_job* j) { Req q = req(RQ_PRED, n, j, NULL, NULL); if (posted_preds_) post(q, j); else submit(q); }
+  void distortion(int, int n, const hop_dist_job* j, uint32_t* o) { Req q = req(RQ_DIST, n, j, NULL, o); submit(q); }
+  void valid_pattern(int, int n, const int32_t* v, uint8_t* o) { Req q = req(RQ_VALID, n, v, NULL, o); submit(q); }
+  void pred_cost(int, int n, const hop_pred_job* j, int kind, uint32_t* o) { Req q = req(RQ_PCOST, n, j, NULL, o, kind); submit(q); }
+  void inter_cu(int, const InterEval& e, const Coder& in, EvalResult& o) { Req q = req(RQ_INTER, 1, &e, &in, &o, e.job.log2_cu, e.skip_res); submit(q); }
+  void intra_cu(int, const IntraEval& e, const Coder& in, EvalResult& o) { Req q = req(RQ_INTRA, 1, &e, &in, &o, e.job.log2_cu, e.part_nxn); submit(q); }
+  void recon_save(int lane, int slot, int x, int y, int size) { Req q = req(RQ_SAVE, 1, NULL, NULL, NULL, x, y, size, lane * 16 + slot); if (posted_mode_ && (posted_kinds_ & 1)) post(q, NULL); else submit(q); }
+  void recon_restore(int lane, int slot, int x, int y, int size) { Req q = req(RQ_RESTORE, 1, NULL, NULL, NULL, x, y, size, lane * 16 + slot); if (posted_mode_ && (posted_kinds_ & 2)) post(q, NULL); else submit(q); }
+  void commit(int, int x, int y, int size) { Req q = req(RQ_COMMIT, 1, NULL, NULL, NULL, x, y, size); if (posted_mode_ && (posted_kinds_ & 4)) post(q, NULL); else submit(q); }
   // everything this fiber has posted is on the device when this returns (a CTU is only counted as retired, and handed to other ranks, behind it)
-  void flush(int lane) { if (!posted_mode_) return; Req q = { RQ_NOP, lane, 1, NULL, NULL, NULL, 0, 0, 0, 0, false, 0, NULL }; submit(q); }
+  void flush() { if (!posted_mode_) return; Req q = req(RQ_NOP, 1, NULL, NULL, NULL); submit(q); }
   void restore_commit(int lane, int slot, int x, int y, int size) {
     if (posted_mode_) { recon_restore(lane, slot, x, y, size); commit(lane, x, y, size); return; }
-    Req q = { RQ_COMMIT, lane, 1, NULL, NULL, NULL, x, y, size, lane * 16 + slot + 1, false, 0, NULL }; submit(q);
+    Req q = req(RQ_COMMIT, 1, NULL, NULL, NULL, x, y, size, lane * 16 + slot + 1); submit(q);
   }
   void wait_counter(std::atomic<int>* ctr, int target) {                // until *ctr >= target (another fiber counts it up)
     if (ctr->load() >= target) return;
@@ -1398,17 +1330,9 @@ class FiberPool : public Backend {
     hop_fiber_switch(&f->sp, sched_[f->worker]);
     if (failed_) throw 1;
   }
-  void wait_step(int st) {                                              // until every wavefront step <= st is finished
-    if (steps_complete.load() >= st) return;
-    Fiber* f = current(); f->wait_step = st;
-    hop_fiber_switch(&f->sp, sched_[f->worker]);
-    if (failed_) throw 1;
-  }
   uint64_t rounds, requests;
   double serve_s = 0;                                                   // wall time inside serve(): packing, issuing, waiting for the device, unpacking
   int tag_shift = 0;
-  std::atomic<int> steps_complete;
-  std::mutex steps_m;                                                   // guards the callers' step counters
  private:
   enum { STACK = 512 * 1024, GUARD = 4096 };
   // a fiber's stack with an inaccessible page below it: an overflow (the recursion of compress_cu under a candidate child) faults instead of corrupting the heap
@@ -1468,7 +1392,6 @@ class FiberPool : public Backend {
         Fiber* f = mine_[w][i];
         if (f->done) { ended |= f->parent != NULL; continue; }
         if (f->req) { if (!f->req->done && !failed_) continue; f->req = NULL; }
-        else if (f->wait_step >= 0) { if (steps_complete.load() < f->wait_step && !failed_) continue; f->wait_step = -1; }
         else if (f->wait_children) { if (f->live_children > 0) continue; f->wait_children = false; }
         else if (f->wait_ctr) { if (f->wait_ctr->load() < f->wait_target && !failed_) continue; f->wait_ctr = NULL; }
         current() = f;
@@ -1492,7 +1415,7 @@ class FiberPool : public Backend {
       lk.unlock();                                                      // (the others only watch gen_ from here on)
       for (int k = 0; k < T_; k++) { pending_.insert(pending_.end(), local_[k].begin(), local_[k].end()); local_[k].clear(); }
       if (left_.load() == 0) { if (posted_mode_ && !pending_.empty() && !failed_) { try { serve_posted(); } catch (...) { failed_ = true; } } finished_ = true; }
-      else if (failed_) { for (Req* r : pending_) (void)r; pending_.clear(); }
+      else if (failed_) pending_.clear();
       else if (!pending_.empty() || !inflight_.empty()) { serve(); idle_rounds_ = 0; }
       else if (++idle_rounds_ > 100000) failed_ = true;                 // rows waiting for a step nobody can finish
       lk.lock();
@@ -1628,13 +1551,83 @@ class FiberPool : public Backend {
   std::mutex bm_; std::condition_variable bcv_; int arrived_; std::atomic<uint64_t> gen_; std::atomic<int> left_; int idle_rounds_;
   std::vector<std::vector<Fiber*> > free_, kids_;
 };
+
+// The steps of a wavefront.  Step s holds the CTUs (r, c) with c + lag * r == s of every picture; a step starts when the previous one has finished, so that its CTUs start
+// together (their requests then carry equal tags and meet in the batches) and every CTU finds the rows above it coded up to column c + lag - 1.  One picture's rows dealt to
+// several ranks (world > 1): this rank's rows only count their CTUs; the exchange fiber moves steps_complete on once the other ranks' CTUs of the step have arrived.
+struct WavefrontSteps {
+  WavefrontSteps(int rows, int cols, int lag, int n_pic, int world, int rank)
+      : rows(rows), cols(cols), lag(lag), n_steps(cols + lag * (rows - 1)), world(world), rank(rank), in_step(n_steps, 0), finished(n_steps), steps_complete(-1), agreed_cancel(0), sync_((size_t)rows * n_pic) {
+    for (int r = 0; r < rows; r++) if (owned(r)) for (int c = 0; c < cols; c++) in_step[step_of(r, c)] += n_pic;
+    for (auto& a : finished) a.store(0);
+  }
+  bool owned(int r) const { return world == 1 || r % world == rank; }
+  int step_of(int r, int c) const { return c + lag * r; }
+  void finish(int step) { std::lock_guard<std::mutex> g(m_); finished[step].fetch_add(1); advance(); }     // one CTU of the step is done
+  // row r codes nothing from column from_c on (the end of the row; a cancel request; a failure): nobody waits for the CTUs it leaves
+  void abandon(int r, int from_c) { std::lock_guard<std::mutex> g(m_); for (int c = from_c; c < cols; c++) finished[step_of(r, c)].fetch_add(1); advance(); }
+  // WaveFrontSynchro: a row's contexts after its second CTU are what the row below starts from, with a fresh bin coder (TEncSlice.cpp:1057-1090, :1158-1161)
+  void store_sync(int p, int r, const Coder& k) { std::lock_guard<std::mutex> g(m_); sync_[(size_t)p * rows + r] = k; }
+  Coder load_sync(int p, int r) { std::lock_guard<std::mutex> g(m_); Coder k = sync_[(size_t)p * rows + r - 1]; coder_set_frac(k, 0); return k; }
+  // rows that are threads: sleep until every step <= `step` is finished; the first failure ends everybody's wait
+  void wait(int step) { std::unique_lock<std::mutex> lk(m_); cv_.wait(lk, [&] { return steps_complete.load() >= step || error; }); if (error) throw 1; }
+  void fail(std::exception_ptr e) { std::lock_guard<std::mutex> g(m_); if (!error) error = e; cv_.notify_all(); }
+  const int rows, cols, lag, n_steps, world, rank;
+  std::vector<int> in_step;                                             // CTUs (of this rank) per step
+  std::vector<std::atomic<int> > finished;                              // ... and how many of them are done (sharded: the exchange fiber waits on it)
+  std::atomic<int> steps_complete;                                      // all steps <= this one are finished
+  std::atomic<int> agreed_cancel;                                       // sharded: a cancel request every rank has seen (set after an exchange)
+  std::exception_ptr error;                                             // what the first failing row threw
+ private:
+  void advance() {                                                      // (lock held)
+    if (world > 1) return;
+    int sc = steps_complete.load();
+    while (sc + 1 < n_steps && finished[sc + 1].load() == in_step[sc + 1]) sc++;
+    steps_complete.store(sc);
+    cv_.notify_all();
+  }
+  std::mutex m_; std::condition_variable cv_; std::vector<Coder> sync_;
+};
+
+// Row r of picture p, CTU by CTU as its steps come up, through `be`.  wait_step(s) returns once every step <= s is finished (and throws when the wavefront has failed);
+// flush, if any, runs after every CTU before it counts.  Honours hop_encode_cancel, counts hop_encode_progress; whatever ends the row early, the rows below are released.
+static void code_row(Encoder& E, int p, int r, int lane, Backend* be, WavefrontSteps& ws, const Coder& init, const std::function<void(int)>& wait_step, const std::function<void()>& flush, uint64_t& n_cand) {
+  const EncConfig& cfg = E.config();
+  CtuWorker* w = NULL;
+  std::exception_ptr err;
+  int c = 0;
+  try {
+    w = new CtuWorker(E, lane, be);
+    Coder k = init;
+    for (; c < ws.cols; c++) {
+      const int st = ws.step_of(r, c);
+      wait_step(st - 1);
+      if (ws.world > 1 ? ws.agreed_cancel.load() != 0 : (cfg.cancel && cfg.cancel->load())) break;   // hop_encode_cancel: this row stops here
+      if (c == 0 && r > 0 && ws.cols >= 2) k = ws.load_sync(p, r);
+      const int a = r * ws.cols + c;
+      E.ctu_entry[a] = k;
+      Coder next; w->compress_ctu(a, k, next);
+      k = next;
+      if (flush) flush();                                               // (posted stash / restore / commit requests of the CTU: done before it counts)
+      if (cfg.progress) cfg.progress->fetch_add(1);
+      if (c == 1) ws.store_sync(p, r, k);
+      if (ws.world > 1) E.ctu_exit[a] = k;                              // (travels to the other ranks)
+      ws.finish(st);
+    }
+  } catch (...) { err = std::current_exception(); ws.fail(err); }      // (before the rows below are released: they then start nothing)
+  ws.abandon(r, c);
+  if (w) n_cand = w->n_cand_;
+  delete w;
+  if (err) std::rethrow_exception(err);
+}
 }  // namespace
 
-void Encoder::encode_frame_wavefront(BatchInner* inner, int lag, int) { Encoder* e = this; wavefront_many(&e, 1, inner, NULL, 0, lag); }
+void Encoder::encode_frame_wavefront(BatchInner* inner, int lag) { Encoder* e = this; wavefront_many(&e, 1, inner, NULL, 0, lag); }
 void Encoder::encode_frame_wavefront_direct(Backend* const* lanes, int n_lanes, int lag) { Encoder* e = this; wavefront_many(&e, 1, NULL, lanes, n_lanes, lag); }
 void Encoder::encode_pictures_wavefront(Encoder* const* encs, int n, BatchInner* inner, int lag, int lane_base, bool begin, int threads) { wavefront_many(encs, n, inner, NULL, 0, lag, lane_base, begin, threads); }
 
-// n pictures of equal geometry side by side (n = 1: one picture): one thread per CTU row of every picture, all of them on one rendezvous
+// n pictures of equal geometry side by side (n = 1: one picture), every CTU row of every picture through code_row.  inner: the rows are fibers of one pool and their requests
+// go to `inner` in batches; else: one thread per row, row r of picture p on lanes[(p * rows + r) % n_lanes]
 void Encoder::wavefront_many(Encoder* const* encs, int n_pic, BatchInner* inner, Backend* const* lanes, int n_lanes, int lag, int lane_base, bool begin, int threads) {
   if (n_pic <= 0 || (!inner && n_lanes <= 0) || lag <= 0) throw 1;
   Encoder& E0 = *encs[0];
@@ -1642,7 +1635,8 @@ void Encoder::wavefront_many(Encoder* const* encs, int n_pic, BatchInner* inner,
   for (int p = 0; p < n_pic; p++) if (!encs[p]->cfg_.wpp || encs[p]->hctu_ != rows || encs[p]->wctu_ != cols) throw 1;
   if (lag > cols) lag = cols;                                          // lag = cols is raster order already
   const int rif = (cols + lag - 1) / lag + 1;                          // rows of one picture that can be in flight together (+ 1 spare)
-  if (lane_base < 0 || lane_base + (long)n_pic * (rif < rows ? rif : rows) > SPINE_LANES) throw 1;
+  const int lanes_per_pic = rif < rows ? rif : rows;
+  if (lane_base < 0 || lane_base + (long)n_pic * lanes_per_pic > SPINE_LANES) throw 1;
   if (begin) { if (inner) inner->begin_frame(); else lanes[0]->begin_frame(); }
   Coder init; memset(&init, 0, sizeof(init));
   hop_cabac_init(&init.r, E0.cfg_.slice_type, E0.cfg_.qp); hop_cabac_cu_init(&init.c, E0.cfg_.slice_type, E0.cfg_.qp); hop_cabac_split_init(init.split, E0.cfg_.slice_type, E0.cfg_.qp);
@@ -1651,82 +1645,32 @@ void Encoder::wavefront_many(Encoder* const* encs, int n_pic, BatchInner* inner,
     for (size_t i = 0; i < E.pic.size(); i++) part_init(E.pic[i], 0);
     std::fill(E.committed.begin(), E.committed.end(), (uint8_t)0);
   }
+  // one picture's rows dealt to several ranks (EncConfig::shard; the batching form only): this process runs the rows r % world == rank and a fiber that, after every
+  // wavefront step, exchanges the step's finished CTUs with the other ranks
+  const int world = (inner && E0.cfg_.shard_world > 1 && E0.cfg_.shard) ? E0.cfg_.shard_world : 1, rank = world > 1 ? E0.cfg_.shard_rank : 0;
+  if (world > 1 && (n_pic != 1 || rank < 0 || rank >= world)) throw 1;
+  WavefrontSteps ws(rows, cols, lag, n_pic, world, rank);
+  auto lane_of = [&](int p, int r) { return lane_base + p * lanes_per_pic + r % rif; };
+  std::vector<uint64_t> cand((size_t)rows * n_pic, 0);
+  uint64_t rounds = 0, requests = 0; double serve_s = 0;
+  std::chrono::steady_clock::time_point run_t0;                        // the wall time of the rows: from the start of the workers / row threads
   if (inner) {                                                          // the batching form: rows as fibers on a few worker threads
     // more workers than the 16 CPUs a GPU box gives a job: a worker spends most of a round asleep at the barrier (measured at 384 pictures: 16 / 24 / 32 workers 275 - 283 /
     // 282 - 287 / 288 CTU/s)
     int T = (int)std::thread::hardware_concurrency(); if (T > 32) T = 32; if (T < 1) T = 1;
     // every round is a barrier over all workers: one picture's 25 rows in flight are served best by about a dozen (12 / 25 / 32 workers: 68.4 / 64.8 / 65.9 CTU/s on one
     // box, the time between the rounds 6.4 / 13.1 / 12.6 s of 54 - 59 s), hundreds of rows (a stack of pictures) by all 32
-    { const int in_flight = n_pic * (rif < rows ? rif : rows), want = in_flight / 2 < 4 ? 4 : in_flight / 2; if (T > want) T = want; }
+    { const int in_flight = n_pic * lanes_per_pic, want = in_flight / 2 < 4 ? 4 : in_flight / 2; if (T > want) T = want; }
     if (threads > 0) T = threads;
     if (const char* e = getenv("HOP_SPINE_THREADS")) { const int v = atoi(e); if (v >= 1 && v <= 64) T = v; }
     if (T > rows * n_pic) T = rows * n_pic;
-    // one picture's rows dealt to several ranks (EncConfig::shard): this process runs the rows r % world == rank and a fiber that, after every wavefront step, exchanges the
-    // step's finished CTUs with the other ranks
-    const int world = (E0.cfg_.shard_world > 1 && E0.cfg_.shard) ? E0.cfg_.shard_world : 1, rank = world > 1 ? E0.cfg_.shard_rank : 0;
-    if (world > 1 && (n_pic != 1 || rank < 0 || rank >= world)) throw 1;
-    auto owned = [&](int r) { return world == 1 || r % world == rank; };
-    if (world > 1) { int mine = 0; for (int r = 0; r < rows; r++) mine += owned(r); if (T > mine + 1) T = mine + 1; if (T < 1) T = 1; }
+    if (world > 1) { int mine = 0; for (int r = 0; r < rows; r++) mine += ws.owned(r); if (T > mine + 1) T = mine + 1; if (T < 1) T = 1; }
     FiberPool pool(inner, T);
     if (E0.cfg_.spec_slots > 0) pool.tag_shift = 20;
-    const int n_steps = cols + lag * (rows - 1);
-    std::vector<int> in_step(n_steps, 0), fin_step(n_steps, 0);
-    for (int r = 0; r < rows; r++) if (owned(r)) for (int c = 0; c < cols; c++) in_step[c + lag * r] += n_pic;
-    std::vector<Coder> sync((size_t)rows * n_pic);
-    std::vector<uint64_t> cand((size_t)rows * n_pic, 0);
-    std::vector<std::atomic<int> > fin_ctr(world > 1 ? n_steps : 0);     // sharded: the step's finished local CTUs (the exchange fiber waits on it)
-    for (auto& a : fin_ctr) a.store(0);
-    std::atomic<int> agreed_cancel(0);                                   // sharded: a cancel request every rank has seen (set after an exchange)
     for (int p = 0; p < n_pic; p++) for (int r = 0; r < rows; r++) {
-      if (!owned(r)) continue;
+      if (!ws.owned(r)) continue;
       pool.add([&, p, r]() {
-        Encoder& E = *encs[p];
-        const int lane = lane_base + p * (rif < rows ? rif : rows) + r % rif;
-        CtuWorker* w = new CtuWorker(E, lane, &pool);
-        int c = 0;
-        try {
-          Coder k = init;
-          for (; c < cols; c++) {
-            const int st = c + lag * r;
-            pool.wait_step(st - 1);
-            if (world > 1 ? agreed_cancel.load() != 0 : (E.cfg_.cancel && E.cfg_.cancel->load())) {   // hop_encode_cancel: this row stops here; nobody waits for the CTUs it leaves uncoded
-              std::lock_guard<std::mutex> g(pool.steps_m);
-              if (world > 1) { for (; c < cols; c++) fin_ctr[c + lag * r].fetch_add(1); break; }
-              for (; c < cols; c++) fin_step[c + lag * r]++;
-              int sc = pool.steps_complete.load();
-              while (sc + 1 < n_steps && fin_step[sc + 1] == in_step[sc + 1]) sc++;
-              pool.steps_complete.store(sc);
-              break;
-            }
-            if (c == 0 && r > 0 && cols >= 2) { std::lock_guard<std::mutex> g(pool.steps_m); k = sync[(size_t)p * rows + r - 1]; coder_set_frac(k, 0); }   // loadContexts (see below)
-            const int a = r * cols + c;
-            E.ctu_entry[a] = k;
-            Coder next; w->compress_ctu(a, k, next);
-            k = next;
-            pool.flush(lane);                                             // (posted stash / restore / commit requests of the CTU: done before it counts)
-            if (E.cfg_.progress) E.cfg_.progress->fetch_add(1);
-            std::lock_guard<std::mutex> g(pool.steps_m);
-            if (c == 1) sync[(size_t)p * rows + r] = k;
-            if (world > 1) { E.ctu_exit[a] = k; fin_ctr[st].fetch_add(1); continue; }   // (the exchange fiber moves steps_complete on)
-            fin_step[st]++;
-            int sc = pool.steps_complete.load();
-            while (sc + 1 < n_steps && fin_step[sc + 1] == in_step[sc + 1]) sc++;
-            pool.steps_complete.store(sc);
-          }
-        } catch (...) {
-          std::lock_guard<std::mutex> g(pool.steps_m);
-          if (world > 1) { for (; c < cols; c++) fin_ctr[c + lag * r].fetch_add(1); }
-          else {
-            for (; c < cols; c++) fin_step[c + lag * r]++;               // after a failure: nobody waits for this row
-            int sc = pool.steps_complete.load();
-            while (sc + 1 < n_steps && fin_step[sc + 1] == in_step[sc + 1]) sc++;
-            pool.steps_complete.store(sc);
-          }
-          cand[(size_t)p * rows + r] = w->n_cand_; delete w;
-          throw;
-        }
-        cand[(size_t)p * rows + r] = w->n_cand_;
-        delete w;
+        code_row(*encs[p], p, r, lane_of(p, r), &pool, ws, init, [&](int st) { pool.wait_counter(&ws.steps_complete, st); }, [&]() { pool.flush(); }, cand[(size_t)p * rows + r]);
       });
     }
     // the exchange fiber: step after step, once this rank's CTUs of the step are finished -- their records out, everybody's in (an all-gather of equally sized slot tables:
@@ -1737,8 +1681,8 @@ void Encoder::wavefront_many(Encoder* const* encs, int n_pic, BatchInner* inner,
       const EncConfig& cfg = E.cfg_;
       auto count_of = [&](int g, int s) { int n = 0; for (int r = g; r < rows; r += world) { const int c = s - lag * r; n += (c >= 0 && c < cols); } return n; };
       std::vector<ShardRec> sendb, recvb;
-      for (int s = 0; s < n_steps; s++) {
-        pool.wait_counter(&fin_ctr[s], in_step[s]);
+      for (int s = 0; s < ws.n_steps; s++) {
+        pool.wait_counter(&ws.finished[s], ws.in_step[s]);
         int slots = 0; for (int g = 0; g < world; g++) slots = std::max(slots, count_of(g, s));
         sendb.assign((size_t)slots + 1, ShardRec()); recvb.resize((size_t)world * (slots + 1));
         memset(&sendb[0], 0, sizeof(ShardRec) * sendb.size());
@@ -1766,80 +1710,35 @@ void Encoder::wavefront_many(Encoder* const* encs, int n_pic, BatchInner* inner,
             E.ctu_cost[a] = t.cost; E.ctu_bits[a] = t.bits; E.ctu_dist[a] = t.dist; E.ctu_rd_fraction[a] = (uint16_t)t.frac; E.ctu_entry[a] = t.entry; E.ctu_exit[a] = t.exit;
             memcpy(&E.pic[(size_t)a * 256], t.parts, sizeof(t.parts));
             for (int yy = y >> 3; yy < (y + h) >> 3; yy++) memset(&E.committed[(size_t)yy * (cfg.pic_w >> 3) + (x >> 3)], 1, w >> 3);
-            if (c == 1) { std::lock_guard<std::mutex> gd(pool.steps_m); sync[r] = t.exit; }
+            if (c == 1) ws.store_sync(0, r, t.exit);
             inner->import_block(x, y + cfg.y_origin, w, h, t.y, t.cb, t.cr);
           }
         }
-        if (any_cancel) { agreed_cancel.store(1); pool.steps_complete.store(n_steps - 1); break; }   // every rank has seen it at this step: the rows stop at their next CTU
-        pool.steps_complete.store(s);
+        if (any_cancel) { ws.agreed_cancel.store(1); ws.steps_complete.store(ws.n_steps - 1); break; }   // every rank has seen it at this step: the rows stop at their next CTU
+        ws.steps_complete.store(s);
       }
     });
-    const std::chrono::steady_clock::time_point run_t0 = std::chrono::steady_clock::now();
+    run_t0 = std::chrono::steady_clock::now();
     pool.run(); pool.print_round_stats();
-    const double run_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - run_t0).count();
-    for (int p = 0; p < n_pic; p++) {
-      Encoder& E = *encs[p];
-      for (int r = 0; r < rows; r++) E.n_candidates += cand[(size_t)p * rows + r];
-      E.batch_rounds = pool.rounds; E.batch_requests = pool.requests; E.batch_serve_s = pool.serve_s; E.batch_run_s = run_s;
-      if (E.trace) for (int a = 0; a < E.n_ctu(); a++) { fputs(E.ctu_trace[a].c_str(), E.trace); E.ctu_trace[a].clear(); }
-    }
-    if (pool.failed()) throw 1;
-    return;
-  }
-  Rendezvous rv(inner, rows * n_pic);
-  // synchronous wavefront: step s holds the CTUs (r, c) with c + lag * r == s of every picture; a step starts when the previous one has finished, so that its CTUs start
-  // together (their requests then carry equal tags and meet in the batches) and every CTU finds the rows above it coded up to column c + lag - 1
-  const int n_steps = cols + lag * (rows - 1);
-  std::vector<int> in_step(n_steps, 0), fin_step(n_steps, 0);
-  for (int r = 0; r < rows; r++) for (int c = 0; c < cols; c++) in_step[c + lag * r] += n_pic;
-  int steps_complete = -1;                                             // all steps <= this one are finished
-  std::vector<Coder> sync((size_t)rows * n_pic);                       // the coder after the second CTU of each row (WaveFrontSynchro)
-  std::vector<uint64_t> cand((size_t)rows * n_pic, 0);
-  std::vector<std::thread> th;
-  for (int p = 0; p < n_pic; p++) for (int r = 0; r < rows; r++) {
-    th.emplace_back([&, p, r]() {
-      Encoder& E = *encs[p];
-      const int lane = p * (rif < rows ? rif : rows) + r % rif;
-      CtuWorker* w = new CtuWorker(E, lane, inner ? (Backend*)&rv : lanes[(p * rows + r) % n_lanes]);
-      int c = 0;
-      try {
-        Coder k = init;
-        for (; c < cols; c++) {
-          const int st = c + lag * r;
-          {
-            std::unique_lock<std::mutex> lk(rv.m);
-            rv.wait_until(lk, [&] { return steps_complete >= st - 1; });
-            if (rv.failed()) break;
-            if (c == 0 && r > 0 && cols >= 2) { k = sync[(size_t)p * rows + r - 1]; coder_set_frac(k, 0); }   // loadContexts: the contexts of the row above after its second CTU, the row's own (fresh) bin coder
-          }
-          const int a = r * cols + c;
-          E.ctu_entry[a] = k;
-          Coder next; w->compress_ctu(a, k, next);
-          k = next;
-          std::unique_lock<std::mutex> lk(rv.m);
-          if (c == 1) sync[(size_t)p * rows + r] = k;
-          fin_step[st]++;
-          while (steps_complete + 1 < n_steps && fin_step[steps_complete + 1] == in_step[steps_complete + 1]) steps_complete++;
-          rv.cv.notify_all();
-        }
-      } catch (...) {}
-      cand[(size_t)p * rows + r] = w->n_cand_;
-      delete w;
-      std::unique_lock<std::mutex> lk(rv.m);
-      for (; c < cols; c++) { fin_step[c + lag * r]++; }               // after a failure: nobody waits for this row
-      while (steps_complete + 1 < n_steps && fin_step[steps_complete + 1] == in_step[steps_complete + 1]) steps_complete++;
-      rv.thread_done(lk);
-      rv.cv.notify_all();
+    rounds = pool.rounds; requests = pool.requests; serve_s = pool.serve_s;
+    if (pool.failed()) ws.fail(std::make_exception_ptr(1));
+  } else {                                                              // rows as threads, each on a backend that serves it at once
+    std::vector<std::thread> th;
+    run_t0 = std::chrono::steady_clock::now();
+    for (int p = 0; p < n_pic; p++) for (int r = 0; r < rows; r++) th.emplace_back([&, p, r]() {
+      try { code_row(*encs[p], p, r, lane_of(p, r), lanes[(p * rows + r) % n_lanes], ws, init, [&](int st) { ws.wait(st); }, nullptr, cand[(size_t)p * rows + r]); }
+      catch (...) {}                                                    // (code_row has recorded it in ws.error; rethrown below, after the join)
     });
+    for (auto& t : th) t.join();
   }
-  for (auto& t : th) t.join();
+  const double run_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - run_t0).count();
   for (int p = 0; p < n_pic; p++) {
     Encoder& E = *encs[p];
     for (int r = 0; r < rows; r++) E.n_candidates += cand[(size_t)p * rows + r];
-    E.batch_rounds = rv.rounds; E.batch_requests = rv.requests;
+    E.batch_rounds = rounds; E.batch_requests = requests; E.batch_serve_s = serve_s; E.batch_run_s = run_s;
     if (E.trace) for (int a = 0; a < E.n_ctu(); a++) { fputs(E.ctu_trace[a].c_str(), E.trace); E.ctu_trace[a].clear(); }
   }
-  if (rv.failed()) throw 1;
+  if (ws.error) std::rethrow_exception(ws.error);
 }
 
 }  // namespace hopspine

@@ -53,8 +53,8 @@ void default_hop_config(EncConfig& c, int pic_w, int pic_h, int qp, int mi_size)
 void default_plain_config(EncConfig& c, int pic_w, int pic_h, int qp, int bit_depth);   // cfg/encoder_intra_main.cfg / encoder_intra_main10.cfg: I slice, no SS / GT
 void finish_config(EncConfig& c);                                                 // TEncSlice::initEncSlice lambda / weights / chroma QP
 
-// HOP_SPINE_POSTED (hop_spine.cpp, FiberPool): requests without an answer do not stop their row.  Level 1, the default, posts what touches nothing another pending request
-// reads (stash, restore, commit); level 2 also posts predictions -- a backend that serves a batch of posted predictions with ONE launch cannot keep two posted predictions of
+// HOP_SPINE_POSTED (hop_spine.cpp, FiberPool; off by default): requests without an answer do not stop their row.  Level 1 posts what touches nothing another pending
+// request reads (restore, commit); level 2 also posts the stash and predictions -- a backend that serves a batch of posted predictions with ONE launch cannot keep two posted predictions of
 // one block in their order, so the device backend clears this flag before it runs and level 2 stays a mode of the CPU spine
 extern bool posted_requests_allowed;
 struct ShardComm {                 // what the caller provides for a picture coded by several ranks (RCCL / gloo / shared memory behind it)
@@ -190,15 +190,16 @@ class Encoder {
  public:
   Encoder(const EncConfig& cfg, Backend* be);
   void encode_frame(int first_ctus = 0);             // the CTUs in raster order (all, or the first `first_ctus`)
-  // CTU rows as a wavefront: row r starts CTU c once row r - 1 has finished CTU c + lag - 1 (lag 5 covers the reach of the SS / GT search); one thread per
-  // row, their requests rendezvous and go to `inner` in batches.  With cfg.wpp the rows' coders are synchronised as WaveFrontSynchro does (TEncSlice.cpp:1027-1051,
-  // :1158-1161) and the result equals the reference run with one substream per row; without it the rows would need the coder of the previous row's END (raster order),
-  // which serialises them: wavefront mode requires cfg.wpp.
-  void encode_frame_wavefront(BatchInner* inner, int lag = 5, int max_rows_in_flight = 0);
-  // the same wavefront without batching: row r talks to lanes[r % n_lanes] directly (backends that run concurrently, e.g. one stream each); at most n_lanes rows in flight
+  // CTU rows as a wavefront: row r starts CTU c once row r - 1 has finished CTU c + lag - 1 (lag 5 covers the reach of the SS / GT search).  The rows
+  // are fibers on a few worker threads; the requests of the rows in flight meet and go to `inner` in batches.  With cfg.wpp the rows' coders are synchronised as
+  // WaveFrontSynchro does (TEncSlice.cpp:1027-1051, :1158-1161) and the result equals the reference run with one substream per row; without it the rows would need the
+  // coder of the previous row's END (raster order), which serialises them: wavefront mode requires cfg.wpp.
+  void encode_frame_wavefront(BatchInner* inner, int lag = 5);
+  // the same wavefront (the same row loop) without batching: one thread per row, row r talking to lanes[r % n_lanes] directly (backends that run concurrently, e.g. one
+  // stream each; with fewer lanes than rows in flight, rows share a lane)
   void encode_frame_wavefront_direct(Backend* const* lanes, int n_lanes, int lag = 5);
-  // n independent pictures of equal geometry (their configurations differ in y_origin: a stacked context) coded side by side: the rows of all of them on one
-  // rendezvous, so that a batch serves CTUs of every picture; each picture's result is what encode_frame_wavefront gives for it alone
+  // n independent pictures of equal geometry (their configurations differ in y_origin: a stacked context) coded side by side: the rows of all of them fibers of one
+  // pool, so that a batch serves CTUs of every picture; each picture's result is what encode_frame_wavefront gives for it alone
   // lane_base: first lane number (stash slots are per lane) when several groups of pictures run side by side on one context, each on a backend of its own;
   // begin = false: the caller has called begin_frame() for all of them
   static void encode_pictures_wavefront(Encoder* const* encs, int n, BatchInner* inner, int lag = 5, int lane_base = 0, bool begin = true, int threads = 0);
@@ -218,7 +219,7 @@ class Encoder {
   uint64_t n_candidates;
   std::vector<std::string> ctu_trace;                // the lines of each CTU while the picture is in flight
   std::vector<uint8_t>  committed;                   // per 8x8 block: its reconstruction is in the SS reference (what TComRdCost::isValidPattern's sentinel test sees)
-  uint64_t batch_rounds, batch_requests;             // wavefront mode: rendezvous rounds and requests served
+  uint64_t batch_rounds, batch_requests;             // wavefront mode with batching: rounds and requests served
   // wavefront mode, the visibility check (CtuWorker::reach_check): a motion search whose window -- the predictor +- the range, plus the block and the GT patch around it --
   // covers samples that the reference, coding the CTUs in raster order, sees otherwise than the wavefront does: (below) committed samples of the CTU rows BELOW the current
   // one (the reference has coded nothing there yet), (above) samples of the rows ABOVE that the wavefront has not coded yet (the reference has).  The lag of 5 CTUs keeps

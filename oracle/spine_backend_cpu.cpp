@@ -270,6 +270,42 @@ static std::vector<uint16_t> g_last_fraction;   // ... and the RD coder's carrie
 static void keep_fraction(const Encoder& e, bool append = false) { if (!append) g_last_fraction.clear(); g_last_fraction.insert(g_last_fraction.end(), e.ctu_rd_fraction.begin(), e.ctu_rd_fraction.end()); }
 static void keep_levels(const CpuBackend& be, bool append = false) { const size_t n = (size_t)((be.W + 63) / 64) * ((be.H + 63) / 64) * 6144; if (!append) g_last_levels.clear(); g_last_levels.insert(g_last_levels.end(), be.coefpic.begin(), be.coefpic.begin() + n); }
 static int spec_slots_env() { const char* e = getenv("HOP_SPEC_SLOTS"); const int v = e ? atoi(e) : 0; return v > 0 && v <= 128 ? v : 0; }
+// the outputs every entry hands back (any may be NULL): per-CTU totals, the finished partition data, the reconstruction before the loop filters
+static void copy_out(const Encoder& e, const CpuBackend& b, double* ctu_cost, uint32_t* ctu_bits, uint32_t* ctu_dist, void* parts, int16_t* rec_y, int16_t* rec_cb, int16_t* rec_cr) {
+  const int n = e.n_ctu(); const size_t w = b.W, h = b.H;
+  if (ctu_cost) memcpy(ctu_cost, &e.ctu_cost[0], n * sizeof(double));
+  if (ctu_bits) memcpy(ctu_bits, &e.ctu_bits[0], n * 4);
+  if (ctu_dist) memcpy(ctu_dist, &e.ctu_dist[0], n * 4);
+  if (parts) memcpy(parts, &e.pic[0], e.pic.size() * sizeof(Part));
+  if (rec_y) memcpy(rec_y, &b.rec[0][0], w * h * 2);
+  if (rec_cb) memcpy(rec_cb, &b.rec[1][0], (w / 2) * (h / 2) * 2);
+  if (rec_cr) memcpy(rec_cr, &b.rec[2][0], (w / 2) * (h / 2) * 2);
+}
+
+// Every request to one backend under a lock that all forwarders of a picture share: CpuBackend is not safe for concurrent callers (its stash is a std::map), and the rows
+// of encode_frame_wavefront_direct call their lanes from threads of their own.  fail_at > 0: the fail_at-th inter_cu of the picture throws (a device error in mid-picture).
+// Only the single forms are forwarded: a batching caller gets BatchInner's defaults, which loop over them (so every evaluation is counted, one at a time), and
+// export_block / import_block are not forwarded at all -- not for a picture dealt to several ranks.
+namespace {
+class LockedForwarder : public BatchInner {
+ public:
+  struct Shared { std::mutex m; long inter_calls = 0, fail_at = 0; };
+  LockedForwarder(Backend* in, Shared* s) : in_(in), s_(s) {}
+  void begin_frame() { Lock g(s_->m); in_->begin_frame(); }
+  void me_search(int lane, int n, const hop_pu_job* jobs, hop_pu_result* res) { Lock g(s_->m); in_->me_search(lane, n, jobs, res); }
+  void pred_inter(int lane, int n, const hop_pred_job* jobs) { Lock g(s_->m); in_->pred_inter(lane, n, jobs); }
+  void distortion(int lane, int n, const hop_dist_job* jobs, uint32_t* out) { Lock g(s_->m); in_->distortion(lane, n, jobs, out); }
+  void valid_pattern(int lane, int n, const int32_t* q, uint8_t* out) { Lock g(s_->m); in_->valid_pattern(lane, n, q, out); }
+  void inter_cu(int lane, const InterEval& e, const Coder& in, EvalResult& out) { Lock g(s_->m); if (++s_->inter_calls == s_->fail_at) throw 1; in_->inter_cu(lane, e, in, out); }
+  void intra_cu(int lane, const IntraEval& e, const Coder& in, EvalResult& out) { Lock g(s_->m); in_->intra_cu(lane, e, in, out); }
+  void recon_save(int lane, int slot, int x, int y, int size) { Lock g(s_->m); in_->recon_save(lane, slot, x, y, size); }
+  void recon_restore(int lane, int slot, int x, int y, int size) { Lock g(s_->m); in_->recon_restore(lane, slot, x, y, size); }
+  void commit(int lane, int x, int y, int size) { Lock g(s_->m); in_->commit(lane, x, y, size); }
+ private:
+  typedef std::lock_guard<std::mutex> Lock;
+  Backend* in_; Shared* s_;
+};
+}
 
 extern "C" {
 
@@ -287,27 +323,23 @@ long hop_spine_cpu_encode(int w, int h, int qp, int mi_size, int first_ctus, con
   if (trace_path && *trace_path) enc.trace = fopen(trace_path, "w");
   enc.encode_frame(first_ctus);
   if (enc.trace) fclose(enc.trace);
-  const int n = enc.n_ctu();
   keep_levels(be); keep_fraction(enc);
-  if (ctu_cost) memcpy(ctu_cost, &enc.ctu_cost[0], n * sizeof(double));
-  if (ctu_bits) memcpy(ctu_bits, &enc.ctu_bits[0], n * 4);
-  if (ctu_dist) memcpy(ctu_dist, &enc.ctu_dist[0], n * 4);
-  if (parts) memcpy(parts, &enc.pic[0], enc.pic.size() * sizeof(Part));
-  if (entry) memcpy(entry, &enc.ctu_entry[0], n * sizeof(Coder));
-  if (rec_y) memcpy(rec_y, &be.rec[0][0], (size_t)w * h * 2);
-  if (rec_cb) memcpy(rec_cb, &be.rec[1][0], (size_t)(w / 2) * (h / 2) * 2);
-  if (rec_cr) memcpy(rec_cr, &be.rec[2][0], (size_t)(w / 2) * (h / 2) * 2);
+  copy_out(enc, be, ctu_cost, ctu_bits, ctu_dist, parts, rec_y, rec_cb, rec_cr);
+  if (entry) memcpy(entry, &enc.ctu_entry[0], enc.n_ctu() * sizeof(Coder));
   return (long)enc.n_candidates;
 }
-// the same with WaveFrontSynchro semantics (one substream per CTU row): lag 0 = the CTUs in raster order on one thread, lag > 0 = the rows as a wavefront of threads whose
+// the same with WaveFrontSynchro semantics (one substream per CTU row): lag 0 = the CTUs in raster order on one thread, lag > 0 = the rows as a wavefront of fibers whose
 // requests are served in batches (what the product does on the GPU)
 // the progress counter and the cancel request of the wavefront (what hop_encode_progress / hop_encode_cancel reach in the product): the next hop_spine_cpu_encode_wpp call
 // is cancelled by a watcher thread as soon as `n` CTUs have been retired (n <= 0: never); hop_spine_cpu_last_progress gives the count the call ended with
-static std::atomic<long> g_progress(0); static std::atomic<int> g_cancel(0); static int g_cancel_after = 0;
+// hop_spine_cpu_fail_at_inter(k): the backend of the next such call throws at the k-th inter_cu it is asked for (k <= 0: never); the call must then return -1
+static std::atomic<long> g_progress(0); static std::atomic<int> g_cancel(0); static int g_cancel_after = 0; static long g_fail_at = 0;
 void hop_spine_cpu_cancel_after(int n) { g_cancel_after = n; }
+void hop_spine_cpu_fail_at_inter(long k) { g_fail_at = k; }
 long hop_spine_cpu_last_progress(void) { return g_progress.load(); }
-long hop_spine_cpu_encode_wpp(int w, int h, int qp, int mi_size, int lag, const int16_t* y, const int16_t* cb, const int16_t* cr, const char* trace_path,
-                              double* ctu_cost, uint32_t* ctu_bits, uint32_t* ctu_dist, void* parts, int16_t* rec_y, int16_t* rec_cb, int16_t* rec_cr, double* rounds_requests) {
+// n_lanes > 0: Encoder::encode_frame_wavefront_direct (one thread per CTU row, no batching) over n_lanes forwarders to the one backend
+static long encode_wpp(int w, int h, int qp, int mi_size, int lag, int n_lanes, const int16_t* y, const int16_t* cb, const int16_t* cr, const char* trace_path,
+                       double* ctu_cost, uint32_t* ctu_bits, uint32_t* ctu_dist, void* parts, int16_t* rec_y, int16_t* rec_cb, int16_t* rec_cr, double* rounds_requests) {
   EncConfig cfg; default_hop_config(cfg, w, h, qp, mi_size); cfg.wpp = 1;
   const int slots = spec_slots_env(); cfg.spec_slots = slots; cfg.slot_pitch = h;
   g_progress.store(0); g_cancel.store(0); cfg.progress = &g_progress; cfg.cancel = &g_cancel;
@@ -318,21 +350,31 @@ long hop_spine_cpu_encode_wpp(int w, int h, int qp, int mi_size, int lag, const 
   CpuBackend be(w, h, 8, y, cb, cr, slots);
   LogBackend* lg = getenv("HOP_SPINE_LOG") ? new LogBackend(&be, getenv("HOP_SPINE_LOG")) : NULL;
   BatchInner* use = lg ? (BatchInner*)lg : (BatchInner*)&be;
+  LockedForwarder::Shared shared; shared.fail_at = g_fail_at; g_fail_at = 0;
+  std::vector<LockedForwarder> fwd((n_lanes > 0 || shared.fail_at > 0) ? (n_lanes > 1 ? n_lanes : 1) : 0, LockedForwarder(use, &shared));
+  std::vector<Backend*> lanes; for (auto& f : fwd) lanes.push_back(&f);
+  if (!fwd.empty()) use = &fwd[0];
   Encoder enc(cfg, use);
   if (trace_path && *trace_path) enc.trace = fopen(trace_path, "w");
-  try { if (lag > 0) enc.encode_frame_wavefront(use, lag); else enc.encode_frame(0); delete lg; } catch (...) { if (enc.trace) fclose(enc.trace); return -1; }
+  try {
+    if (n_lanes > 0) enc.encode_frame_wavefront_direct(lanes.data(), n_lanes, lag); else if (lag > 0) enc.encode_frame_wavefront(use, lag); else enc.encode_frame(0);
+    delete lg;
+  } catch (...) { if (enc.trace) fclose(enc.trace); return -1; }
   if (enc.trace) fclose(enc.trace);
-  const int n = enc.n_ctu();
   keep_levels(be); keep_fraction(enc);
-  if (ctu_cost) memcpy(ctu_cost, &enc.ctu_cost[0], n * sizeof(double));
-  if (ctu_bits) memcpy(ctu_bits, &enc.ctu_bits[0], n * 4);
-  if (ctu_dist) memcpy(ctu_dist, &enc.ctu_dist[0], n * 4);
-  if (parts) memcpy(parts, &enc.pic[0], enc.pic.size() * sizeof(Part));
-  if (rec_y) memcpy(rec_y, &be.rec[0][0], (size_t)w * h * 2);
-  if (rec_cb) memcpy(rec_cb, &be.rec[1][0], (size_t)(w / 2) * (h / 2) * 2);
-  if (rec_cr) memcpy(rec_cr, &be.rec[2][0], (size_t)(w / 2) * (h / 2) * 2);
+  copy_out(enc, be, ctu_cost, ctu_bits, ctu_dist, parts, rec_y, rec_cb, rec_cr);
   if (rounds_requests) { rounds_requests[0] = (double)enc.batch_rounds; rounds_requests[1] = (double)enc.batch_requests; }
   return (long)enc.n_candidates;
+}
+long hop_spine_cpu_encode_wpp(int w, int h, int qp, int mi_size, int lag, const int16_t* y, const int16_t* cb, const int16_t* cr, const char* trace_path,
+                              double* ctu_cost, uint32_t* ctu_bits, uint32_t* ctu_dist, void* parts, int16_t* rec_y, int16_t* rec_cb, int16_t* rec_cr, double* rounds_requests) {
+  return encode_wpp(w, h, qp, mi_size, lag, 0, y, cb, cr, trace_path, ctu_cost, ctu_bits, ctu_dist, parts, rec_y, rec_cb, rec_cr, rounds_requests);
+}
+// the same picture through the wavefront without batching (what hop_encode_frame does with streams > 1): the same outputs
+long hop_spine_cpu_encode_wpp_direct(int w, int h, int qp, int mi_size, int lag, int n_lanes, const int16_t* y, const int16_t* cb, const int16_t* cr, const char* trace_path,
+                                     double* ctu_cost, uint32_t* ctu_bits, uint32_t* ctu_dist, void* parts, int16_t* rec_y, int16_t* rec_cb, int16_t* rec_cr, double* rounds_requests) {
+  if (n_lanes < 1 || lag < 1) return -1;
+  return encode_wpp(w, h, qp, mi_size, lag, n_lanes, y, cb, cr, trace_path, ctu_cost, ctu_bits, ctu_dist, parts, rec_y, rec_cb, rec_cr, rounds_requests);
 }
 // ---- one picture's CTU rows dealt to several ranks (EncConfig::shard) ----
 // (a) `world` ranks as threads of this process, each with a backend (a "device") of its own, exchanging through an in-process all-gather: every rank must end with the whole
@@ -375,15 +417,7 @@ long hop_spine_cpu_encode_sharded(int w, int h, int qp, int mi_size, int lag, in
   stop.store(1); watcher.join();
   long rc = 0;
   for (int g = 0; g < world; g++) { if (!ok[g]) rc = -1; if (retired_per_rank) retired_per_rank[g] = prog[g].load(); }
-  Encoder& e = *encs[take]; CpuBackend& b = *bes[take];
-  const int n = e.n_ctu();
-  if (ctu_cost) memcpy(ctu_cost, &e.ctu_cost[0], n * sizeof(double));
-  if (ctu_bits) memcpy(ctu_bits, &e.ctu_bits[0], n * 4);
-  if (ctu_dist) memcpy(ctu_dist, &e.ctu_dist[0], n * 4);
-  if (parts) memcpy(parts, &e.pic[0], e.pic.size() * sizeof(Part));
-  if (rec_y) memcpy(rec_y, &b.rec[0][0], (size_t)w * h * 2);
-  if (rec_cb) memcpy(rec_cb, &b.rec[1][0], (size_t)(w / 2) * (h / 2) * 2);
-  if (rec_cr) memcpy(rec_cr, &b.rec[2][0], (size_t)(w / 2) * (h / 2) * 2);
+  copy_out(*encs[take], *bes[take], ctu_cost, ctu_bits, ctu_dist, parts, rec_y, rec_cb, rec_cr);
   if (rc == 0) for (int g = 0; g < world; g++) rc += (long)encs[g]->n_candidates;
   for (auto e2 : encs) delete e2;
   for (auto b2 : bes) delete b2;
@@ -400,10 +434,7 @@ long hop_spine_cpu_encode_shard_rank(int w, int h, int qp, int mi_size, int lag,
   CpuBackend be(w, h, 8, y, cb, cr, 0);
   Encoder enc(cfg, &be);
   try { enc.encode_frame_wavefront(&be, lag); } catch (...) { return -1; }
-  const int n = enc.n_ctu();
-  if (ctu_cost) memcpy(ctu_cost, &enc.ctu_cost[0], n * sizeof(double));
-  if (parts) memcpy(parts, &enc.pic[0], enc.pic.size() * sizeof(Part));
-  if (rec_y) memcpy(rec_y, &be.rec[0][0], (size_t)w * h * 2);
+  copy_out(enc, be, ctu_cost, NULL, NULL, parts, rec_y, NULL, NULL);
   return (long)enc.n_candidates;
 }
 
@@ -460,15 +491,8 @@ long hop_spine_cpu_encode_plain(int w, int h, int qp, int bit_depth, const int16
   if (trace_path && *trace_path) enc.trace = fopen(trace_path, "w");
   enc.encode_frame(0);
   if (enc.trace) fclose(enc.trace);
-  const int n = enc.n_ctu();
   keep_levels(be); keep_fraction(enc);
-  if (ctu_cost) memcpy(ctu_cost, &enc.ctu_cost[0], n * sizeof(double));
-  if (ctu_bits) memcpy(ctu_bits, &enc.ctu_bits[0], n * 4);
-  if (ctu_dist) memcpy(ctu_dist, &enc.ctu_dist[0], n * 4);
-  if (parts) memcpy(parts, &enc.pic[0], enc.pic.size() * sizeof(Part));
-  if (rec_y) memcpy(rec_y, &be.rec[0][0], (size_t)w * h * 2);
-  if (rec_cb) memcpy(rec_cb, &be.rec[1][0], (size_t)(w / 2) * (h / 2) * 2);
-  if (rec_cr) memcpy(rec_cr, &be.rec[2][0], (size_t)(w / 2) * (h / 2) * 2);
+  copy_out(enc, be, ctu_cost, ctu_bits, ctu_dist, parts, rec_y, rec_cb, rec_cr);
   return (long)enc.n_candidates;
 }
 // the levels of the picture(s) the last entry coded: per CTU 6144 TCoeff in the reference's layout, as hop_levels_download hands them out; returns the count

@@ -75,6 +75,24 @@ def test_encode_frame_wavefront_equals_the_reference_with_wavefront_synchro(W, H
     ctx.close()
 
 
+def test_encode_frame_wavefront_on_views_equals_the_reference_with_wavefront_synchro():
+    """streams > 1: the wavefront without batching -- one thread per CTU row, each row's requests on a view of the context (a stream of its own).  Two CTU rows on three
+    views, so no two rows share a view; lag 5, no candidate slots; against the same golden as the batched form above"""
+    hp = _hp()
+    G = np.load(os.path.join(ROOT, "tests", "golden", "encoder_spine.npz"))
+    W, H, seed = 192, 128, 7
+    Y, Cb, Cr = frame(W, H, seed, False)
+    ctx = hp.Context(W, H)
+    ctx.upload_orig(Y, Cb, Cr)
+    with tempfile.TemporaryDirectory() as td:
+        tp = os.path.join(td, "t.txt")
+        cost, bits, dist, parts, nc = ctx.encode_frame(32, 16, 0, tp, wpp=1, wavefront_lag=5, streams=3)
+        text = open(tp, "rb").read()
+    check_against_golden(G, key_of(W, H, seed, False) + "_wpp", cost, bits, dist, parts.view(np.dtype(parts.dtype.descr)), text)
+    print(key_of(W, H, seed, False), "wpp lag 5 on 3 views", nc, "candidates")
+    ctx.close()
+
+
 @pytest.mark.parametrize("bd,qp", PLAIN)
 def test_encode_frame_plain_intra_configurations(bd, qp):
     """BASELINE configs 1 and 4 on the GPU: I slices at 8 bit (QP 32) and 10 bit (QP 22 / 27 / 32 / 37) against the reference run with the plain intra configurations"""
