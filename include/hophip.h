@@ -742,7 +742,12 @@ int hop_psnr(hop_ctx* ctx, uint64_t* ssd, double* psnr);
  * schedule 0: the CTUs run in levels of a dependency graph (hop_decode_schedule), one launch per level, every CTU seeing the SS-reference state raster order gives it;
  * schedule 1: raster order, one CTU per launch (the yardstick).  Both give the same picture.  One picture per context: a stacked or sharded context is refused; so is
  * malformed partition data (inconsistent CU fields, directions outside 0..34 / DM, transform depths out of range, a vector or GT footprint outside the padded plane
- * and its guard rows, SS/GT CUs with plain_intra, the HOP configuration at a bit depth other than 8), before anything is enqueued.  Synchronous. */
+ * and its guard rows, SS/GT CUs with plain_intra, the HOP configuration at a bit depth other than 8), before anything is enqueued.  Synchronous.
+ * Part sizes: an intra CU is 2Nx2N, or NxN at 8x8; an SS / GT CU is 2Nx2N, 2NxN or Nx2N, or an AMP shape from 16x16 up (NxN is refused, as the syntax has none).
+ * cbf: bit tr_idx of the TU's first unit; the 4x4 chroma block of four 4x4 luma TUs reads bit tr_idx - 1 (its 8x8 node's) and the transform-skip flag of the first unit.
+ * Levels: clipped to 16 bits first, as TComTrQuant::xDeQuant does.  The reference's Int arithmetic defines |level| * (invQuantScales[qp % 6] << (qp / 6)) + add only
+ * below 2^31; for every QP this entry accepts (scaled QP 0 .. 63) that holds for the whole 16-bit range -32768 .. 32767 (the largest scale is 57 << 10), so every
+ * level has a defined result and the output is the reference's for all of them. */
 typedef struct {
   int32_t qp, cb_qp_offset, cr_qp_offset;   /* slice QP and pps_cb_qp_offset / pps_cr_qp_offset */
   int32_t plain_intra;                      /* as hop_enc_params.plain_intra: 1 an I slice at the context's bit depth, 0 the HOP configuration (SS / GT CUs, 8 bit) */

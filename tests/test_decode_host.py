@@ -27,6 +27,9 @@ def case_id(c):
     return "%s_%dx%d_%s_%s" % c
 
 
+SPINE_REC = {}          # case -> the three planes the CPU spine reconstructed, kept by coded() for tests/test_refdecode_cpu.py
+
+
 @functools.lru_cache(maxsize=None)
 def coded(case):
     """(W, H, parts, levels) of the CPU spine's run on the case's picture"""
@@ -35,19 +38,20 @@ def coded(case):
     n = ((W + 63) // 64) * ((H + 63) // 64)
     if kind == "frame":
         Y, Cb, Cr = frame(W, H, a, b)
-        parts = run_cpu(L, W, H, Y, Cb, Cr)[3]
+        out = run_cpu(L, W, H, Y, Cb, Cr)
     elif kind == "wpp":
         Y, Cb, Cr = lenslet(W, H, 16, a)
-        parts = run_cpu_wpp(L, W, H, Y, Cb, Cr, b)[3]
+        out = run_cpu_wpp(L, W, H, Y, Cb, Cr, b)
     elif kind == "mi15":
         Y, Cb, Cr = lenslet(W, H, 15, a)
-        parts = run_cpu(L, W, H, Y, Cb, Cr, mi=15)[3] if b is None else run_cpu_wpp(L, W, H, Y, Cb, Cr, b, mi=15)[3]
+        out = run_cpu(L, W, H, Y, Cb, Cr, mi=15) if b is None else run_cpu_wpp(L, W, H, Y, Cb, Cr, b, mi=15)
     else:                                                             # the plain intra configurations, at 8 and 10 bit
         rng = np.random.RandomState(9)
         Y, Cb, Cr = lenslet(W, H, 16, 9)
         if a > 8:
             Y, Cb, Cr = (np.clip(p.astype(np.int32) * 4 + rng.randint(0, 4, p.shape), 0, 1023).astype(np.int16) for p in (Y, Cb, Cr))
-        parts = run_cpu_plain(L, W, H, Y, Cb, Cr, b, a)[3]
+        out = run_cpu_plain(L, W, H, Y, Cb, Cr, b, a)
+    parts, SPINE_REC[case] = out[3], out[4]
     levels = cpu_last_levels(L, n)
     return W, H, np.ascontiguousarray(parts).view(hophip.CU_PART_DTYPE).reshape(n, 256), levels
 
