@@ -433,16 +433,30 @@ def test_rqt_encoder_calls(hp):
     ctx.close()
 
 
-def test_rqt_random_vs_oracle(hp):
-    """hop_rqt against the restatement (pinned inside the reference encoder) where the recorded calls do not go: 8 and 10 bit, QP 20..42,
-    sign hiding and transform skip on and off, the inter_split_flag tree, every CU size, smooth and spiky residuals, context states of all
-    five slice types with a non-zero carried fraction"""
+def _rqt_smooth_content(rng, cu, bd):
+    """original and prediction (Y | Cb | Cr blocks each) of one CU of test_rqt_random_vs_oracle: a mid-grey prediction, smooth and spiky residuals"""
+    mid = 1 << (bd - 1)
+    amp = float(rng.choice([4, 12, 40])) * (1 << (bd - 8))
+    yy, xx = np.mgrid[0:cu, 0:cu]
+    ry = amp * np.sin(xx * rng.uniform(0.1, 0.9) + rng.uniform(0, 3)) * np.cos(yy * rng.uniform(0.1, 0.9)) + rng.normal(0, amp / 4, (cu, cu))
+    if rng.random() < 0.5:                                                     # spikes: transform skip territory
+        m = rng.random((cu, cu)) < 0.06; ry[m] += rng.choice([-1, 1], int(m.sum())) * 6 * amp
+    ry = np.clip(np.rint(ry), -(1 << bd) + 1, (1 << bd) - 1).astype(np.int16)
+    rc = [np.clip(np.rint(ry[::2, ::2] * s + rng.normal(0, amp / 6, (cu // 2, cu // 2))), -(1 << bd) + 1, (1 << bd) - 1).astype(np.int16) for s in (0.5, -0.4)]
+    pred = [np.full((cu, cu), mid, np.int16), np.full((cu // 2, cu // 2), mid, np.int16), np.full((cu // 2, cu // 2), mid, np.int16)]
+    return [(p + r).astype(np.int16) for p, r in zip(pred, [ry] + rc)], pred
+
+
+def rqt_random_check(hp, bd, content=_rqt_smooth_content, qps=None):
+    """32 CUs through hop_rqt + hop_rqt_finish in one call against the restatement; content(rng, cu, bd) gives a CU's original and prediction, qps (if given) replaces the
+    drawn QPs in turn.  Returns how many CUs had a tree two levels deep, chose transform skip, lost the root-cbf-zero test, kept a level of magnitude >= 1024."""
     import ctypes
     from goldutil import oracle_rqt, RQT_CFG
-    for bd in (8, 10):
+    if True:
         rng = np.random.default_rng(40 + bd)
         W, H = 512, 256
         org = [np.full((H, W), 1 << (bd - 1), np.int16), np.full((H // 2, W // 2), 1 << (bd - 1), np.int16), np.full((H // 2, W // 2), 1 << (bd - 1), np.int16)]
+        prd = [a.copy() for a in org]
         n = 32
         jobs = np.zeros(n, hp.RQT_JOB_DTYPE); cfgs = np.zeros(n, RQT_CFG); snaps = np.zeros((n, hp.CABAC_CTX_BYTES), np.uint8); resis = []
         ctx = hp.Context(W, H, bd)
@@ -450,16 +464,13 @@ def test_rqt_random_vs_oracle(hp):
         for i in range(n):
             lg = 3 + (i % 4); cu = 1 << lg; n2 = cu * cu
             x, y = 64 * (i % 8), 64 * (i // 8)
-            amp = float(rng.choice([4, 12, 40])) * (1 << (bd - 8))
-            yy, xx = np.mgrid[0:cu, 0:cu]
-            ry = amp * np.sin(xx * rng.uniform(0.1, 0.9) + rng.uniform(0, 3)) * np.cos(yy * rng.uniform(0.1, 0.9)) + rng.normal(0, amp / 4, (cu, cu))
-            if rng.random() < 0.5:                                                     # spikes: transform skip territory
-                m = rng.random((cu, cu)) < 0.06; ry[m] += rng.choice([-1, 1], int(m.sum())) * 6 * amp
-            ry = np.clip(np.rint(ry), -(1 << bd) + 1, (1 << bd) - 1).astype(np.int16)
-            rc = [np.clip(np.rint(ry[::2, ::2] * s + rng.normal(0, amp / 6, (cu // 2, cu // 2))), -(1 << bd) + 1, (1 << bd) - 1).astype(np.int16) for s in (0.5, -0.4)]
-            resis.append(np.concatenate([ry.ravel(), rc[0].ravel(), rc[1].ravel()]))
-            org[0][y:y + cu, x:x + cu] += ry; org[1][y // 2:(y + cu) // 2, x // 2:(x + cu) // 2] += rc[0]; org[2][y // 2:(y + cu) // 2, x // 2:(x + cu) // 2] += rc[1]
-            qp = int(rng.integers(20, 43)) + 6 * (bd - 8); lam = 0.57 * 2.0 ** ((qp - 6 * (bd - 8) - 12) / 3.0); w = float(rng.choice([1.0, 1.26, 1.59]))
+            o3, p3 = content(rng, cu, bd)
+            resis.append(np.concatenate([(o - p).astype(np.int16).ravel() for o, p in zip(o3, p3)]))
+            for k, (o, p) in enumerate(zip(o3, p3)):
+                sl = (slice(y, y + cu), slice(x, x + cu)) if k == 0 else (slice(y // 2, (y + cu) // 2), slice(x // 2, (x + cu) // 2))
+                org[k][sl] = o; prd[k][sl] = p
+            qp = int(rng.integers(20, 43))
+            qp = (qp if qps is None else qps[i % len(qps)]) + 6 * (bd - 8); lam = 0.57 * 2.0 ** ((qp - 6 * (bd - 8) - 12) / 3.0); w = float(rng.choice([1.0, 1.26, 1.59]))
             c = cfgs[i]
             c["log2_cu"], c["qp"], c["bit_depth_y"], c["bit_depth_c"] = lg, (qp, qp - 1, qp - 2), bd, bd
             c["sign_hide"], c["use_ts"], c["log2_max_tu"] = int(rng.integers(0, 2)), int(rng.integers(0, 2)), 5
@@ -475,13 +486,13 @@ def test_rqt_random_vs_oracle(hp):
             left = int(rng.integers(0, 32768)); snaps[i, 150], snaps[i, 151] = left & 255, left >> 8
         ctx.upload_orig(*org)
         for comp in range(3):
-            ctx.plane_upload("pred", comp, np.full(org[comp].shape, 1 << (bd - 1), np.int16))
+            ctx.plane_upload("pred", comp, prd[comp])
         res, co, cx = ctx.rqt(jobs, snaps)
         for comp in range(3):
             ctx.plane_upload("recon", comp, np.zeros(org[comp].shape, np.int16))
         res3, co3, fin3 = ctx.rqt_finish(jobs, res, co, cx)
         rec = [ctx.recon_download(k) for k in range(3)]
-        off = 0; deep = ts = zeros = 0
+        off = 0; deep = ts = zeros = big = 0
         for i in range(n):
             cu = 1 << int(cfgs[i]["log2_cu"]); n2 = cu * cu; x, y = int(jobs[i]["x"]), int(jobs[i]["y"])
             o_i = np.concatenate([org[0][y:y + cu, x:x + cu].ravel(), org[1][y // 2:(y + cu) // 2, x // 2:(x + cu) // 2].ravel(), org[2][y // 2:(y + cu) // 2, x // 2:(x + cu) // 2].ravel()])
@@ -491,7 +502,7 @@ def test_rqt_random_vs_oracle(hp):
             assert int(fin3[i, 0]) == tail["root"] and [int(v) for v in fin3[i, 1:]] == tail["d3"] and np.array_equal(got_rec, tail["rec"]), (bd, i, cfgs[i], fin3[i], tail["root"], tail["d3"])
             g3 = np.concatenate([res3[i]["tr_idx"][None, :], res3[i]["cbf"], res3[i]["tskip"]])
             assert np.array_equal(g3[:, :n2 // 16], tail["arr"][:, :n2 // 16]) and np.array_equal(co3[off:off + n2 * 3 // 2], tail["fin"]), (bd, i)
-            zeros += int(tail["root"] == 0)
+            zeros += int(tail["root"] == 0); big += int(np.abs(tail["fin"]).max() >= 1024)
             cu = 1 << int(cfgs[i]["log2_cu"]); m = cu * cu * 3 // 2; parts = cu * cu // 16
             r = res[i]
             assert (float(r["cost"]), int(r["bits"]), int(r["dist"]), int(r["zero_dist"])) == want, (bd, i, cfgs[i], r["cost"], r["bits"], r["dist"], want)
@@ -499,8 +510,17 @@ def test_rqt_random_vs_oracle(hp):
             assert np.array_equal(got[:, :parts], arr[:, :parts]) and np.array_equal(co[off:off + m], fin), (bd, i, cfgs[i])
             assert np.array_equal(cx[i, :150], ocx) and (int(cx[i, 150]) | (int(cx[i, 151]) << 8)) == ofr, (bd, i)
             deep += int(arr[0, :parts].max() >= 2); ts += int(arr[4:, :parts].any()); off += m
-        assert deep >= 2 and ts >= 2 and zeros >= 1, (bd, deep, ts, zeros)
         ctx.close()
+        return dict(deep=deep, ts=ts, zeros=zeros, big=big)
+
+
+def test_rqt_random_vs_oracle(hp):
+    """hop_rqt against the restatement (pinned inside the reference encoder) where the recorded calls do not go: 8 and 10 bit, QP 20..42,
+    sign hiding and transform skip on and off, the inter_split_flag tree, every CU size, smooth and spiky residuals, context states of all
+    five slice types with a non-zero carried fraction"""
+    for bd in (8, 10):
+        st = rqt_random_check(hp, bd)
+        assert st["deep"] >= 2 and st["ts"] >= 2 and st["zeros"] >= 1, (bd, st)
 
 
 def test_cu_bits_encoder_calls(hp):
@@ -744,8 +764,22 @@ def test_intra_rqt_encoder_calls(hp):
     ctx.close()
 
 
-def _irqt_random_cases(hp, L, bd):
-    """72 random PUs, each in its own 192 x 192 tile (CU at +64): pictures, jobs, syntax, options, restatement configs, snapshots, availability tables"""
+def _irqt_smooth_content(rng, cu, bd):
+    """a smooth random field over the CU and its neighbourhood (references further away predict worse: splitting pays), the picture around the CU = the field plus
+    coding noise; on half of the PUs isolated spikes on top (transform-skip territory).  Returns the field and the picture, (2 cu + 1)^2 each, from (-1, -1) of the CU"""
+    mid = 1 << (bd - 1); top = (1 << bd) - 1
+    amp = float(rng.choice([20, 50, 90])) * (1 << (bd - 8)); Wn = 2 * cu + 1
+    f = gaussian_filter(rng.normal(0, 1, (Wn + 16, Wn + 16)), float(rng.choice([1.5, 3, 6])))[8:-8, 8:-8]
+    f = mid + amp * f / max(1e-9, float(np.abs(f).max()))
+    if rng.random() < 0.5:
+        m = rng.random(f.shape) < 0.05; f[m] += rng.choice([-1, 1], int(m.sum())) * 2.5 * amp
+    f = np.clip(np.rint(f), 0, top).astype(np.int16)
+    return f, np.clip(f + rng.integers(-2, 3, f.shape), 0, top)
+
+
+def _irqt_random_cases(hp, L, bd, content=_irqt_smooth_content, qps=None):
+    """72 random PUs, each in its own 192 x 192 tile (CU at +64): pictures, jobs, syntax, options, restatement configs, snapshots, availability tables.  content(rng, cu, bd)
+    gives the original around a CU and the picture around it; qps (if given) replaces the drawn QPs in turn"""
     from goldutil import RQT_CFG
     rng = np.random.default_rng(70 + bd)
     T = 192; G = 9; W = H = T * G; n = 72
@@ -759,17 +793,11 @@ def _irqt_random_cases(hp, L, bd):
         lg = 3 + (i % 4); cu = 1 << lg
         nxn = int(lg == 3 and rng.random() < 0.6)
         x0, y0 = (i % G) * T + 64, (i // G) * T + 64
-        # a smooth random field over the CU and its neighbourhood (references further away predict worse: splitting pays), the picture around the CU = the field plus
-        # coding noise; on half of the PUs isolated spikes on top (transform-skip territory)
-        amp = float(rng.choice([20, 50, 90])) * (1 << (bd - 8)); Wn = 2 * cu + 1
-        f = gaussian_filter(rng.normal(0, 1, (Wn + 16, Wn + 16)), float(rng.choice([1.5, 3, 6])))[8:-8, 8:-8]
-        f = mid + amp * f / max(1e-9, float(np.abs(f).max()))
-        if rng.random() < 0.5:
-            m = rng.random(f.shape) < 0.05; f[m] += rng.choice([-1, 1], int(m.sum())) * 2.5 * amp
-        f = np.clip(np.rint(f), 0, top).astype(np.int16)
+        f, around = content(rng, cu, bd)
         Y[y0:y0 + cu, x0:x0 + cu] = f[1:1 + cu, 1:1 + cu]
-        R[y0 - 1:y0 + 2 * cu, x0 - 1:x0 + 2 * cu] = np.clip(f + rng.integers(-2, 3, f.shape), 0, top)
-        qp = int(rng.integers(20, 43)) + 6 * (bd - 8); lam = 0.57 * 2.0 ** ((qp - 6 * (bd - 8) - 12) / 3.0)
+        R[y0 - 1:y0 + 2 * cu, x0 - 1:x0 + 2 * cu] = around
+        qp = int(rng.integers(20, 43))
+        qp = (qp if qps is None else qps[i % len(qps)]) + 6 * (bd - 8); lam = 0.57 * 2.0 ** ((qp - 6 * (bd - 8) - 12) / 3.0)
         c = cfgs[i]
         c["log2_cu"], c["qp"], c["bit_depth_y"], c["bit_depth_c"] = lg, (qp, qp, qp), bd, bd
         c["sign_hide"], c["use_ts"], c["log2_max_tu"] = int(rng.integers(0, 2)), int(rng.random() < 0.7), 5
@@ -796,22 +824,20 @@ def _irqt_random_cases(hp, L, bd):
     return W, H, Y, R, jobs, syn, opts, cfgs, snaps, cus, avs
 
 
-def test_intra_rqt_random_vs_oracle(hp):
-    """hop_intra_rqt against the restatement (pinned inside the reference encoder) where the recorded calls do not go: 8 and 10 bit, QP 20..42, sign hiding / transform
-    skip / TransformSkipFast / strong smoothing on and off, every CU size, 2Nx2N and the four PUs of NxN, bCheckFirst on and off, deeper trees than the encoder's
-    configuration allows, random neighbour availability per node, smooth and sharp content, context states of all slice types with a carried fraction.  72 PUs per bit
-    depth in one call (several classes), each in its own tile."""
+def intra_rqt_random_check(hp, bd, **kw):
+    """the 72 PUs of _irqt_random_cases(hp, L, bd, **kw) through hop_intra_rqt in one call against the restatement.  Returns how many PUs had a tree two levels deep,
+    chose transform skip, kept one transform where a split was allowed, kept a level of magnitude >= 1024."""
     import ctypes
     from goldutil import oracle_intra_rqt, RQT_CFG, INTRA_SYN
-    for bd in (8, 10):
-        W, H, Y, R, jobs, syn, opts, cfgs, snaps, cus, avs = _irqt_random_cases(hp, hp.load(), bd)
+    if True:
+        W, H, Y, R, jobs, syn, opts, cfgs, snaps, cus, avs = _irqt_random_cases(hp, hp.load(), bd, **kw)
         n = len(jobs); mid = 1 << (bd - 1)
         ctx = hp.Context(W, H, bd)
         ctx.upload_orig(Y, np.full((H // 2, W // 2), mid, np.int16), np.full((H // 2, W // 2), mid, np.int16))
         ctx.plane_upload("recon", 0, R)
         res, coef, cx, cu_out = ctx.intra_rqt(jobs, syn, opts, snaps, cus)
         R2 = ctx.recon_download(0)
-        o = 0; deep = ts = single_over_split = 0
+        o = 0; deep = ts = single_over_split = big = 0
         for i in range(n):
             c = cfgs[i]; cu = 1 << int(c["log2_cu"]); Wn = 2 * cu + 1; parts = (cu // 4) ** 2
             x0, y0 = int(jobs[i]["x"]), int(jobs[i]["y"]); d0, p0 = int(syn[i]["tr_depth"]), int(syn[i]["part"]); np_ = parts >> (2 * d0)
@@ -829,12 +855,23 @@ def test_intra_rqt_random_vs_oracle(hp):
             assert np.array_equal(cx[i, :150], ocoder[:150]) and (int(cx[i, 150]) | (int(cx[i, 151]) << 8)) == (int.from_bytes(ocoder[152:160].tobytes(), "little") & 32767), tag
             assert np.array_equal(cu_out[i], ocu), tag
             R[y0 - 1:y0 - 1 + Wn, x0 - 1:x0 - 1 + Wn] = win.reshape(Wn, Wn)
+            big += int(np.abs(fin[16 * p0:16 * (p0 + np_)]).max() >= 1024)
             deep += int(arr[0, p0:p0 + np_].max() >= d0 + 2); ts += int(arr[4, p0:p0 + np_].any())
             lg = int(c["log2_cu"]); single_over_split += int(arr[0, p0] == d0 and lg - d0 > int(c["log2_min_tu_in_cu"]) and not nd[2] and lg - d0 <= 5)
             o += cu * cu * 3 // 2
         assert np.array_equal(R, R2), bd
-        assert deep >= 4 and ts >= 3 and single_over_split >= 4, (bd, deep, ts, single_over_split)
         ctx.close()
+        return dict(deep=deep, ts=ts, single_over_split=single_over_split, big=big)
+
+
+def test_intra_rqt_random_vs_oracle(hp):
+    """hop_intra_rqt against the restatement (pinned inside the reference encoder) where the recorded calls do not go: 8 and 10 bit, QP 20..42, sign hiding / transform
+    skip / TransformSkipFast / strong smoothing on and off, every CU size, 2Nx2N and the four PUs of NxN, bCheckFirst on and off, deeper trees than the encoder's
+    configuration allows, random neighbour availability per node, smooth and sharp content, context states of all slice types with a carried fraction.  72 PUs per bit
+    depth in one call (several classes), each in its own tile."""
+    for bd in (8, 10):
+        st = intra_rqt_random_check(hp, bd)
+        assert st["deep"] >= 4 and st["ts"] >= 3 and st["single_over_split"] >= 4, (bd, st)
 
 
 def test_intra_luma_search_encoder_calls(hp):
@@ -890,12 +927,13 @@ def test_intra_luma_search_encoder_calls(hp):
     ctx.close()
 
 
-def test_intra_luma_search_random_vs_oracle(hp):
-    """hop_intra_luma_search against the restatement (pinned inside the reference encoder) on the random CUs of test_intra_rqt_random_vs_oracle (8 and 10 bit, every CU size,
-    NxN, deeper trees, random availability) with random neighbour directions and rough-search flags: 72 CUs per bit depth in one call (several classes)"""
+def intra_luma_search_random_check(hp, bd, on_cu=None, **kw):
+    """the 72 CUs of _irqt_random_cases(hp, L, bd, **kw), with random neighbour directions and rough-search flags, through hop_intra_luma_search in one call against the
+    restatement.  Returns how many CUs were NxN, ended with the final tree better than the candidate's, kept a level of magnitude >= 1024.  on_cu (if given) is called
+    per CU with what the restatement was fed (cfg, syntax, ts_fast, strong, search job, availability, original, picture window before the search, coder, CU contexts)."""
     from goldutil import oracle_intra_luma_search, INTRA_SYN
-    for bd in (8, 10):
-        W, H, Y, R, jobs, syn, opts, cfgs, snaps, cus, avs = _irqt_random_cases(hp, hp.load(), bd)
+    if True:
+        W, H, Y, R, jobs, syn, opts, cfgs, snaps, cus, avs = _irqt_random_cases(hp, hp.load(), bd, **kw)
         n = len(jobs); mid = 1 << (bd - 1)
         rng = np.random.default_rng(90 + bd)
         sj = np.zeros(n, hp.INTRA_SEARCH_JOB_DTYPE)
@@ -909,7 +947,7 @@ def test_intra_luma_search_random_vs_oracle(hp):
         ctx.plane_upload("recon", 0, R)
         sres, res, coef, reco = ctx.intra_luma_search(jobs, syn, opts, sj, snaps, cus)
         R2 = ctx.recon_download(0)
-        o = ro = 0; final_better = nxn_n = 0
+        o = ro = 0; final_better = nxn_n = big = 0
         for i in range(n):
             c = cfgs[i]; cu = 1 << int(c["log2_cu"]); Wn = 2 * cu + 1; parts = (cu // 4) ** 2; npu = 4 if syn[i]["part_nxn"] else 1
             x0, y0 = int(jobs[i]["x"]), int(jobs[i]["y"])
@@ -924,12 +962,22 @@ def test_intra_luma_search_random_vs_oracle(hp):
             assert [int(v) for v in sres[i]["best_dir"][:npu]] == best[:npu] and [int(v) for v in sres[i]["n_cand"][:npu]] == ncand[:npu] and int(sres[i]["dist"]) == dist, (tag, sres[i], best, ncand, dist)
             assert np.array_equal(res[i]["tr_idx"][:parts], arr[0, :parts]) and np.array_equal(res[i]["cbf"][0][:parts], arr[1, :parts]) and np.array_equal(res[i]["tskip"][0][:parts], arr[4, :parts]), tag
             assert np.array_equal(coef[o:o + cu * cu], ocoef) and np.array_equal(reco[ro:ro + cu * cu], oreco), tag
+            if on_cu: on_cu(c, osyn[0], nd[0], nd[1], sj[i], avs[i], Y[y0:y0 + cu, x0:x0 + cu], R[y0 - 1:y0 - 1 + Wn, x0 - 1:x0 - 1 + Wn].copy(), np.frombuffer(coder, np.uint8), cus[i])
             R[y0 - 1:y0 - 1 + Wn, x0 - 1:x0 - 1 + Wn] = win.reshape(Wn, Wn)
+            big += int(np.abs(ocoef).max() >= 1024)
             final_better += int(not np.array_equal(oreco.reshape(cu, cu), win.reshape(Wn, Wn)[1:1 + cu, 1:1 + cu])); nxn_n += int(npu == 4)
             o += cu * cu * 3 // 2; ro += cu * cu
         assert np.array_equal(R, R2), bd
-        assert nxn_n >= 4, (bd, nxn_n, final_better)
         ctx.close()
+        return dict(nxn=nxn_n, final_better=final_better, big=big)
+
+
+def test_intra_luma_search_random_vs_oracle(hp):
+    """hop_intra_luma_search against the restatement (pinned inside the reference encoder) on the random CUs of test_intra_rqt_random_vs_oracle (8 and 10 bit, every CU size,
+    NxN, deeper trees, random availability) with random neighbour directions and rough-search flags: 72 CUs per bit depth in one call (several classes)"""
+    for bd in (8, 10):
+        st = intra_luma_search_random_check(hp, bd)
+        assert st["nxn"] >= 4, (bd, st)
 
 
 def test_intra_chroma_search_encoder_calls(hp):
@@ -987,13 +1035,25 @@ def test_intra_chroma_search_encoder_calls(hp):
     ctx.close()
 
 
-def test_intra_chroma_search_random_vs_oracle(hp):
-    """hop_intra_luma_search followed by hop_intra_chroma_search on the random CUs of the luma tests (8 and 10 bit, every CU size, NxN, deeper trees, random availability),
-    with chroma planes of their own, chroma quantisers / lambdas / distortion weights that differ per plane, TransformSkipFast on and off: the chroma search against the
-    restatement fed with the same luma arrays"""
+def _chroma_smooth_content(rng, cu, bd):
+    """one chroma plane around a CU, as _irqt_smooth_content gives the luma: the field and the picture, (cu + 1)^2 each, from (-1, -1) of the CU's chroma block"""
+    mid = 1 << (bd - 1); top = (1 << bd) - 1; Wn = cu + 1
+    amp = float(rng.choice([15, 40, 80])) * (1 << (bd - 8))
+    f = gaussian_filter(rng.normal(0, 1, (Wn + 16, Wn + 16)), float(rng.choice([1.0, 2.5, 5])))[8:-8, 8:-8]
+    f = mid + amp * f / max(1e-9, float(np.abs(f).max()))
+    if rng.random() < 0.5:
+        m = rng.random(f.shape) < 0.06; f[m] += rng.choice([-1, 1], int(m.sum())) * 2.5 * amp
+    f = np.clip(np.rint(f), 0, top).astype(np.int16)
+    return f, np.clip(f + rng.integers(-2, 3, f.shape), 0, top)
+
+
+def intra_chroma_search_random_check(hp, bd, chroma_content=_chroma_smooth_content, **kw):
+    """the 72 CUs of _irqt_random_cases(hp, L, bd, **kw), with chroma planes from chroma_content(rng, cu, bd), through hop_intra_luma_search and hop_intra_chroma_search; the
+    chroma search against the restatement fed with the same luma arrays.  Returns how many CUs chose transform skip in chroma, the set of winning modes, how many CUs
+    kept a chroma level of magnitude >= 1024 and the largest magnitude of all."""
     from goldutil import oracle_intra_chroma_search, INTRA_SYN
-    for bd in (8, 10):
-        W, H, Y, R, jobs, syn, opts, cfgs, snaps, cus, avs = _irqt_random_cases(hp, hp.load(), bd)
+    if True:
+        W, H, Y, R, jobs, syn, opts, cfgs, snaps, cus, avs = _irqt_random_cases(hp, hp.load(), bd, **kw)
         n = len(jobs); mid = 1 << (bd - 1); top = (1 << bd) - 1
         rng = np.random.default_rng(110 + bd)
         sj = np.zeros(n, hp.INTRA_SEARCH_JOB_DTYPE)
@@ -1003,14 +1063,9 @@ def test_intra_chroma_search_random_vs_oracle(hp):
             cu = 1 << int(jobs[i]["log2_cu"]); half = cu // 2; Wn = cu + 1; x0, y0 = int(jobs[i]["x"]) // 2, int(jobs[i]["y"]) // 2
             sj[i]["sqrt_lambda"] = float(np.sqrt(jobs[i]["lambda_rd"])); sj[i]["num_full_rd"] = 8 if (cu >> int(syn[i]["part_nxn"])) <= 8 else 3
             for k in range(2):
-                amp = float(rng.choice([15, 40, 80])) * (1 << (bd - 8))
-                f = gaussian_filter(rng.normal(0, 1, (Wn + 16, Wn + 16)), float(rng.choice([1.0, 2.5, 5])))[8:-8, 8:-8]
-                f = mid + amp * f / max(1e-9, float(np.abs(f).max()))
-                if rng.random() < 0.5:
-                    m = rng.random(f.shape) < 0.06; f[m] += rng.choice([-1, 1], int(m.sum())) * 2.5 * amp
-                f = np.clip(np.rint(f), 0, top).astype(np.int16)
+                f, around = chroma_content(rng, cu, bd)
                 C[k][y0:y0 + half, x0:x0 + half] = f[1:1 + half, 1:1 + half]
-                RC[k][y0 - 1:y0 - 1 + Wn, x0 - 1:x0 - 1 + Wn] = np.clip(f + rng.integers(-2, 3, f.shape), 0, top)
+                RC[k][y0 - 1:y0 - 1 + Wn, x0 - 1:x0 - 1 + Wn] = around
             qp = int(jobs[i]["qp_scaled"][0]); w = (float(rng.choice([1.0, 1.26, 1.59])), float(rng.choice([1.0, 1.26])))
             jobs[i]["qp_scaled"] = (qp, max(6 * (bd - 8), qp - int(rng.integers(0, 4))), max(6 * (bd - 8), qp - int(rng.integers(0, 6))))
             lam = float(jobs[i]["lambda_rd"]); jobs[i]["lambda_rdoq"] = (lam, lam / w[0], lam / w[1]); jobs[i]["dist_weight"] = w
@@ -1023,7 +1078,7 @@ def test_intra_chroma_search_random_vs_oracle(hp):
         syn2 = syn.copy(); syn2["luma_dir"] = sres["best_dir"]
         cres, res2, coef, reco = ctx.intra_chroma_search(jobs, syn2, opts, res, snaps, cus)
         R2 = [ctx.recon_download(1), ctx.recon_download(2)]
-        o = ro = 0; ts = 0; modes = set()
+        o = ro = 0; ts = big = peak = 0; modes = set()
         for i in range(n):
             c = cfgs[i]; cu = 1 << int(c["log2_cu"]); half = cu // 2; Wn = cu + 1; parts = (cu // 4) ** 2
             x0, y0 = int(jobs[i]["x"]) // 2, int(jobs[i]["y"]) // 2
@@ -1038,11 +1093,20 @@ def test_intra_chroma_search_random_vs_oracle(hp):
             assert np.array_equal(res2[i]["cbf"][1:, :parts], arr[2:4, :parts]) and np.array_equal(res2[i]["tskip"][1:, :parts], arr[5:7, :parts]), tag
             assert np.array_equal(coef[o + cu * cu:o + cu * cu * 3 // 2], ocoef) and np.array_equal(reco[ro:ro + cu * cu // 2], oreco), tag
             for k in range(2): RC[k][y0 - 1:y0 - 1 + Wn, x0 - 1:x0 - 1 + Wn] = owin.reshape(2, Wn, Wn)[k]
-            ts += int(arr[5:7, :parts].any()); modes.add(mode)
+            ts += int(arr[5:7, :parts].any()); modes.add(mode); big += int(np.abs(ocoef).max() >= 1024); peak = max(peak, int(np.abs(ocoef).max()))
             o += cu * cu * 3 // 2; ro += cu * cu // 2
         assert np.array_equal(RC[0], R2[0]) and np.array_equal(RC[1], R2[1]), bd
-        assert ts >= 3 and len(modes) >= 4, (bd, ts, modes)
         ctx.close()
+        return dict(ts=ts, modes=modes, big=big, peak=peak)
+
+
+def test_intra_chroma_search_random_vs_oracle(hp):
+    """hop_intra_luma_search followed by hop_intra_chroma_search on the random CUs of the luma tests (8 and 10 bit, every CU size, NxN, deeper trees, random availability),
+    with chroma planes of their own, chroma quantisers / lambdas / distortion weights that differ per plane, TransformSkipFast on and off: the chroma search against the
+    restatement fed with the same luma arrays"""
+    for bd in (8, 10):
+        st = intra_chroma_search_random_check(hp, bd)
+        assert st["ts"] >= 3 and len(st["modes"]) >= 4, (bd, st)
 
 
 def test_intra_cu_total_bits_encoder_calls(hp):
