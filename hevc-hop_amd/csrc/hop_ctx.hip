@@ -21,31 +21,187 @@ int hop_set_err(hop_ctx* c, int code, const char* fmt, ...) {
 #define HIPCHK(c, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) \
   return hop_set_err((c), HOP_ERR_DEVICE, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
 
+// ---------------------------------------------------------------------------------------------
+// what the entry points below share: device buffers that grow on demand, the lanes, the staging arena of the host-array entries, grouping jobs by class, the validators
+// ---------------------------------------------------------------------------------------------
+// Makes *buf hold at least `need` bytes.  When it has to grow, the stream is synchronised first (queued kernels may still use the old block) and need + slack bytes are allocated.
+static int hop_reserve(hop_ctx* c, void** buf, size_t* have, size_t need, size_t slack) {
+  if (need <= *have) return HOP_OK;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (*buf) HIPCHK(c, hipFree(*buf));
+  *buf = nullptr; *have = 0;
+  HIPCHK(c, hipSetDevice(c->device));                                    // (the calling thread's current device may be another context's)
+  HIPCHK(c, hipMalloc(buf, need + slack));
+  *have = need + slack;
+  return HOP_OK;
+}
 int hop_scratch(hop_ctx* c, size_t bytes, void** out) {
-  if (bytes > c->scratch_bytes) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->scratch) HIPCHK(c, hipFree(c->scratch));
-    c->scratch = nullptr; c->scratch_bytes = 0;
-    size_t want = bytes + bytes / 4 + 4096;
-    HIPCHK(c, hipSetDevice(c->device));                                  // (the calling thread's current device may be another context's)
-    HIPCHK(c, hipMalloc(&c->scratch, want));
-    c->scratch_bytes = want;
-  }
+  int r = hop_reserve(c, &c->scratch, &c->scratch_bytes, bytes, bytes / 4 + 4096); if (r) return r;
   *out = c->scratch;
   return HOP_OK;
 }
 static int hop_stage(hop_ctx* c, size_t bytes, void** out) {
-  if (bytes > c->stage_bytes) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->stage) HIPCHK(c, hipFree(c->stage));
-    c->stage = nullptr; c->stage_bytes = 0;
-    size_t want = bytes + bytes / 4 + 4096;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMalloc(&c->stage, want));
-    c->stage_bytes = want;
-  }
+  int r = hop_reserve(c, &c->stage, &c->stage_bytes, bytes, bytes / 4 + 4096); if (r) return r;
   *out = c->stage;
   return HOP_OK;
+}
+// the quadtree searches' state buffer; it is free again once a search's kernels are queued (same stream), so the stages of a chain share it
+static int rqt_reserve(hop_ctx* c, size_t bytes) { return hop_reserve(c, &c->rqt_buf, &c->rqt_bytes, bytes, bytes / 8); }
+static int walk_reserve(hop_ctx* c, size_t bytes) { return hop_reserve(c, &c->walk_buf, &c->walk_bytes, bytes, bytes / 4); }
+
+// The streams and events of a context: its own stream, the extra lanes' streams and join events, the fork event.
+// The context's own stream -- the spine's short requests: predictions, searches, block copies -- runs at the highest priority, the views' streams (the candidate
+// evaluations, hundreds of long workgroups in flight) at the lowest: without it a 10 us prediction kernel waits for a free compute unit behind them (measured on the
+// 7728-wide picture: 0.15 ms -> 0.03 ms per prediction request, 27 -> 35 CTU/s).  HOP_STREAM_PRIO=0 turns it off.
+static hipError_t create_lanes(hop_ctx* c, unsigned stream_flags, bool highest_priority) {
+  int prio_lo = 0, prio_hi = 0; (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+  const char* f = getenv("HOP_STREAM_PRIO");
+  hipError_t e = (f && f[0] == '0') ? hipStreamCreateWithFlags(&c->stream, stream_flags) : hipStreamCreateWithPriority(&c->stream, stream_flags, highest_priority ? prio_hi : prio_lo);
+  for (int k = 0; k < HOP_MAX_LANES - 1 && e == hipSuccess; k++) {
+    e = hipStreamCreateWithFlags(&c->xlane[k].stream, stream_flags);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_join[k], hipEventDisableTiming);
+  }
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming);
+  return e;
+}
+
+// While it lives the context works on extra lane k: that lane's stream and work areas stand in for the context's own.
+struct lane_scope {
+  hop_lane &own, &other;
+  lane_scope(hop_ctx* c, int k) : own(*c), other(c->xlane[k]) { std::swap(own, other); }
+  ~lane_scope() { std::swap(own, other); }
+  lane_scope(const lane_scope&) = delete;
+};
+
+// body(0) .. body(n_items - 1), item i on lane i % HOP_MAX_LANES: the items are independent chains of kernels, each lane a stream with work areas of its own.  The extra
+// lanes this call uses start behind what is queued on the context's stream, and the stream continues behind them.  Stops issuing at the first item that fails.
+template <class Body>
+static int run_on_lanes(hop_ctx* c, int n_items, const char* what, Body body) {
+  const int n_fork = std::min(n_items, HOP_MAX_LANES) - 1;
+  if (n_fork > 0) HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
+  for (int k = 0; k < n_fork; k++) HIPCHK(c, hipStreamWaitEvent(c->xlane[k].stream, c->ev_fork, 0));
+  bool used[HOP_MAX_LANES - 1] = { false, false, false };
+  int rc = HOP_OK;
+  for (int i = 0; i < n_items && rc == HOP_OK; i++) {
+    const int lane = i % HOP_MAX_LANES;
+    if (lane == 0) { rc = body(i); continue; }
+    lane_scope on(c, lane - 1);
+    rc = body(i);
+    used[lane - 1] = true;
+  }
+  for (int k = 0; k < HOP_MAX_LANES - 1; k++) {
+    if (!used[k]) continue;
+    hipError_t e = hipEventRecord(c->ev_join[k], c->xlane[k].stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, c->ev_join[k], 0);
+    if (e != hipSuccess && rc == HOP_OK) rc = hop_set_err(c, HOP_ERR_DEVICE, "%s: stream join: %s", what, hipGetErrorString(e));
+  }
+  return rc;
+}
+
+// The staging area of one host-array call.  The entry declares its segments in the order they lie in the area, each 256-byte aligned: in() is uploaded from the host,
+// out() is room for results, zero() is room that is cleared; end_mark() is the aligned end.  commit() makes the one reservation (it may reallocate, so nothing is copied
+// before it) and issues the uploads and clears on c->stream in the order they were declared.  After it a[seg] is the segment's device pointer, download() copies a segment
+// back and sync() waits for the stream.  A segment's type and element count are stated once, at its declaration; every copy takes its size from there.
+struct stage_arena {
+  template <class T> struct seg { int i; };
+  explicit stage_arena(hop_ctx* ctx) : c(ctx) {}
+  template <class T> seg<T> out(size_t m) {
+    const size_t off = (end + 255) & ~(size_t)255;
+    segs.push_back({ off, m * sizeof(T) }); end = off + m * sizeof(T);
+    return seg<T>{ (int)segs.size() - 1 };
+  }
+  template <class T> seg<T> in(const T* src, size_t m) { seg<T> s = out<T>(m); ops.push_back({ s.i, s.i, src }); return s; }
+  template <class T> seg<T> zero(size_t m) { seg<T> s = out<T>(m); ops.push_back({ s.i, s.i, nullptr }); return s; }
+  seg<char> end_mark() { return out<char>(0); }
+  template <class T> void zero_span(seg<T> first, seg<char> last) { ops.push_back({ first.i, last.i, nullptr }); }   // first .. last in one clear, the padding between them included
+  int commit(size_t slack) {
+    void* st; int r = hop_stage(c, end + slack, &st); if (r) return r;
+    base = (char*)st;
+    for (const op& o : ops) {
+      const extent& s = segs[o.first];
+      if (o.src) HIPCHK(c, hipMemcpyAsync(base + s.off, o.src, s.bytes, hipMemcpyHostToDevice, c->stream));
+      else HIPCHK(c, hipMemsetAsync(base + s.off, 0, segs[o.last].off + segs[o.last].bytes - s.off, c->stream));
+    }
+    return HOP_OK;
+  }
+  template <class T> T* operator[](seg<T> s) const { return (T*)(base + segs[s.i].off); }
+  template <class T> int upload(seg<T> s, const T* src) { HIPCHK(c, hipMemcpyAsync(base + segs[s.i].off, src, segs[s.i].bytes, hipMemcpyHostToDevice, c->stream)); return HOP_OK; }   // an in() that is not due at commit()
+  template <class T> int download(T* dst, seg<T> s) { HIPCHK(c, hipMemcpyAsync(dst, base + segs[s.i].off, segs[s.i].bytes, hipMemcpyDeviceToHost, c->stream)); return HOP_OK; }
+  int sync() { HIPCHK(c, hipStreamSynchronize(c->stream)); return HOP_OK; }
+ private:
+  struct extent { size_t off, bytes; };
+  struct op { int first, last; const void* src; };                      // src: upload segment `first`; no src: clear first .. last
+  hop_ctx* c; char* base = nullptr; size_t end = 0;
+  std::vector<extent> segs; std::vector<op> ops;
+};
+
+// body(idx) once per class of the jobs 0 .. n-1 -- i and k are of one class when same(i, k) --, the classes in the order of their first jobs, idx a class's jobs in ascending order
+template <class Same, class Body>
+static int for_each_class(int n, Same same, Body body) {
+  std::vector<char> done(n, 0);
+  for (int first = 0; first < n; first++) {
+    if (done[first]) continue;
+    std::vector<int> idx;
+    for (int i = first; i < n; i++) if (!done[i] && same(first, i)) { done[i] = 1; idx.push_back(i); }
+    int r = body(idx); if (r) return r;
+  }
+  return HOP_OK;
+}
+// The per-job arrays of a class in class order and back: job i's block is `len` elements at src + off[i] (without off: at src + i * len); packed, block t of the
+// class is at t * stride (stride 0: len).
+template <class T>
+static std::vector<T> gather(const T* src, const std::vector<int>& idx, size_t len = 1, const size_t* off = nullptr) {
+  std::vector<T> v(idx.size() * len);
+  for (size_t t = 0; t < idx.size(); t++) std::copy_n(src + (off ? off[idx[t]] : idx[t] * len), len, v.begin() + t * len);
+  return v;
+}
+template <class T>
+static void scatter(T* dst, const std::vector<int>& idx, const T* v, size_t len = 1, const size_t* off = nullptr, size_t stride = 0) {
+  for (size_t t = 0; t < idx.size(); t++) std::copy_n(v + t * (stride ? stride : len), len, dst + (off ? off[idx[t]] : idx[t] * len));
+}
+
+// A legal class of CUs: size 8..64, transform sizes 4..32, the smallest transform of the CU within them, at most three levels below the CU and the largest at most one.
+static bool rqt_class_ok(const hop_rqt_job& j) {
+  return j.log2_cu >= 3 && j.log2_cu <= 6 && j.log2_max_tu >= 2 && j.log2_max_tu <= 5 && j.log2_min_tu_in_cu >= 2 && j.log2_min_tu_in_cu <= j.log2_max_tu &&
+         j.log2_cu - j.log2_min_tu_in_cu <= 3 && j.log2_cu - j.log2_max_tu <= 1;
+}
+// same CU size, transform-tree limits and transform-skip switch: the part of the class key every grouped entry has
+static bool same_tree(const hop_rqt_job& a, const hop_rqt_job& b) {
+  return a.log2_cu == b.log2_cu && a.log2_max_tu == b.log2_max_tu && a.log2_min_tu_in_cu == b.log2_min_tu_in_cu && !a.use_ts == !b.use_ts;
+}
+// the CU of a legal size, aligned to it and inside the picture
+static bool cu_rect_ok(const hop_ctx* c, const hop_rqt_job& j) {
+  if (j.log2_cu < 3 || j.log2_cu > 6) return false;
+  const int S = 1 << j.log2_cu;
+  return j.x >= 0 && j.y >= 0 && (j.x & (S - 1)) == 0 && (j.y & (S - 1)) == 0 && j.x + S <= c->pic_w && j.y + S <= c->pic_h;
+}
+static size_t cu_coeffs(int log2_cu) { return ((size_t)3 << (2 * log2_cu)) >> 1; }   // levels of a CU: luma + two chroma blocks
+// every state of the coder snapshots (and of the CU-level ones, where the entry takes them) is a CABAC state
+static bool ctx_states_ok(hop_ctx* c, int n_ctx, const hop_cabac_ctx* ctx_in, const hop_cabac_cu_ctx* cu_ctx_in) {
+  for (int k = 0; k < n_ctx; k++) {
+    for (int i = 0; i < 150; i++) if (ctx_in[k].state[i] > 127) { hop_set_err(c, HOP_ERR_ARG, "context snapshot %d: state %d out of range", k, i); return false; }
+    for (int i = 0; cu_ctx_in && i < 19; i++) if (cu_ctx_in[k].state[i] > 127) { hop_set_err(c, HOP_ERR_ARG, "CU context snapshot %d: state %d out of range", k, i); return false; }
+  }
+  return true;
+}
+// An intra block of a plane, sh = 0 luma / 1 chroma: size (in the plane's samples) 4..64 / 4..32, its position (in luma samples) on the plane's 4-sample grid, inside the plane.
+static bool intra_block_ok(const hop_ctx* c, const hop_intra_job& j, int sh) {
+  const int N = j.size, grid = (4 << sh) - 1;
+  return (N == 4 || N == 8 || N == 16 || N == 32 || (N == 64 && !sh)) && j.x >= 0 && j.y >= 0 && !(j.x & grid) && !(j.y & grid) &&
+         (j.x >> sh) + N <= (c->pic_w >> sh) && (j.y >> sh) + N <= (c->pic_h >> sh);
+}
+// An available neighbour unit (4 luma samples: 4 / 2 samples of the plane) must lie inside the picture (the reference derives availability from existing CUs): units
+// 0 .. 2U-1 up the left edge from below, 2U the corner, 2U+1 .. 4U along the top.  *bad is the first unit that does not.
+static bool intra_neighbours_ok(const hop_ctx* c, const hop_intra_job& j, int sh, int* bad) {
+  const int unit = 4 >> sh, U = j.size / unit, x = j.x >> sh, y = j.y >> sh, w = c->pic_w >> sh, h = c->pic_h >> sh;
+  for (int u = 0; u < 4 * U + 1; u++) if (j.flags[u]) {
+    bool ok;
+    if (u < 2 * U) ok = x > 0 && y + unit * (2 * U - 1 - u) + unit <= h;
+    else if (u == 2 * U) ok = x > 0 && y > 0;
+    else ok = y > 0 && x + unit * (u - 2 * U - 1) + unit <= w;
+    if (!ok) { *bad = u; return false; }
+  }
+  return true;
 }
 
 extern "C" {
@@ -76,14 +232,7 @@ int hop_ctx_create(hop_ctx** out, int pic_w, int pic_h, int bit_depth_y, int bit
   }
   size_t ny = (size_t)pic_w * pic_h, nc = ny >> 2;
   size_t sy = (size_t)c->stride_y * (pic_h + 2 * HOP_MARGIN_Y), sc = (size_t)c->stride_c * ((pic_h >> 1) + 2 * HOP_MARGIN_C);
-  // The context's own stream -- the spine's short requests: predictions, searches, block copies -- runs at the highest priority, the views' streams (the candidate
-  // evaluations, hundreds of long workgroups in flight) at the lowest: without it a 10 us prediction kernel waits for a free compute unit behind them (measured on the
-  // 7728-wide picture: 0.15 ms -> 0.03 ms per prediction request, 27 -> 35 CTU/s).  HOP_STREAM_PRIO=0 turns it off.
-  int prio_lo = 0, prio_hi = 0; (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-  const bool prio = !(getenv("HOP_STREAM_PRIO") && getenv("HOP_STREAM_PRIO")[0] == '0');
-  hipError_t e = prio ? hipStreamCreateWithPriority(&c->stream, hipStreamDefault, prio_hi) : hipStreamCreate(&c->stream);
-  for (int k = 0; k < HOP_MAX_LANES - 1 && e == hipSuccess; k++) { e = hipStreamCreate(&c->xstream[k]); if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_join[k], hipEventDisableTiming); }
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming);
+  hipError_t e = create_lanes(c, hipStreamDefault, true);
   { const char* f = getenv("HOP_LANES"); c->lanes = f ? atoi(f) : 2; if (c->lanes < 1) c->lanes = 1; if (c->lanes > HOP_MAX_LANES) c->lanes = HOP_MAX_LANES; }
   if (e == hipSuccess) e = hipMalloc((void**)&c->org_y, ny * 2);
   if (e == hipSuccess) e = hipMalloc((void**)&c->org_cb, nc * 2);
@@ -130,13 +279,7 @@ int hop_ctx_create_view(hop_ctx* parent, hop_ctx** out) {
   for (int k = 0; k < 3; k++) { c->ss_alloc[k] = parent->ss_alloc[k]; c->ss_buf[k] = parent->ss_buf[k]; c->ss00[k] = parent->ss00[k]; c->pred[k] = parent->pred[k]; c->rec[k] = parent->rec[k]; }
   c->entropy_bits = parent->entropy_bits; c->rdoq_scans = parent->rdoq_scans; c->have_orig = parent->have_orig; c->stash = parent->stash; c->stash_slots = parent->stash_slots; c->coefpic = parent->coefpic; c->coef_stash = parent->coef_stash;
   hipError_t e = hipSetDevice(c->device);
-  if (e == hipSuccess) {
-    int prio_lo = 0, prio_hi = 0; (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    const bool prio = !(getenv("HOP_STREAM_PRIO") && getenv("HOP_STREAM_PRIO")[0] == '0');
-    e = prio ? hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, prio_lo) : hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-  }
-  for (int k = 0; k < HOP_MAX_LANES - 1 && e == hipSuccess; k++) { e = hipStreamCreateWithFlags(&c->xstream[k], hipStreamNonBlocking); if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_join[k], hipEventDisableTiming); }
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming);
+  if (e == hipSuccess) e = create_lanes(c, hipStreamNonBlocking, false);
   if (e != hipSuccess) { hop_set_err(parent, HOP_ERR_DEVICE, "hop_ctx_create_view: %s", hipGetErrorString(e)); hop_ctx_destroy(c); return HOP_ERR_DEVICE; }
   *out = c;
   return HOP_OK;
@@ -191,11 +334,10 @@ void hop_ctx_destroy(hop_ctx* c) {
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   for (int k = 0; k < HOP_MAX_LANES - 1; k++) {
-    if (c->xstream[k]) (void)hipStreamDestroy(c->xstream[k]);
+    const hop_lane& x = c->xlane[k];
+    if (x.stream) (void)hipStreamDestroy(x.stream);
     if (c->ev_join[k]) (void)hipEventDestroy(c->ev_join[k]);
-    if (c->xscratch[k]) (void)hipFree(c->xscratch[k]);
-    if (c->xrqt_buf[k]) (void)hipFree(c->xrqt_buf[k]);
-    if (c->xwalk_buf[k]) (void)hipFree(c->xwalk_buf[k]);
+    for (void* p : { x.scratch, x.rqt_buf, x.walk_buf }) if (p) (void)hipFree(p);
   }
   if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
   free(c);
@@ -262,18 +404,11 @@ int hop_ssref_commit_cus(hop_ctx* c, int n, const int32_t* rect4, const int16_t*
   std::vector<int32_t> rr(rect4, rect4 + 4 * (size_t)n);
   size_t tot = 0;
   for (int i = 0; i < n; i++) { rr[4 * i + 3] = (int32_t)tot; tot += (size_t)rr[4 * i + 2] * rr[4 * i + 2]; }
-  size_t bytes_r = (size_t)n * 16, bytes_y = tot * 2, bytes_c = (tot >> 2) * 2;
-  size_t o_y = (bytes_r + 255) & ~(size_t)255, o_cb = (o_y + bytes_y + 255) & ~(size_t)255, o_cr = (o_cb + bytes_c + 255) & ~(size_t)255;
-  void* st; r = hop_stage(c, o_cr + bytes_c, &st); if (r) return r;
-  char* b = (char*)st;
-  HIPCHK(c, hipMemcpyAsync(b, rr.data(), bytes_r, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(b + o_y, rec_y, bytes_y, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(b + o_cb, rec_cb, bytes_c, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(b + o_cr, rec_cr, bytes_c, hipMemcpyHostToDevice, c->stream));
-  r = hop_launch_ssref_commit(c, n, (const int32_t*)b, (const int16_t*)(b + o_y), (const int16_t*)(b + o_cb), (const int16_t*)(b + o_cr), 1);
-  if (r) return r;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return HOP_OK;
+  stage_arena a(c);
+  auto dr = a.in(rr.data(), rr.size()); auto dy = a.in(rec_y, tot); auto dcb = a.in(rec_cb, tot >> 2); auto dcr = a.in(rec_cr, tot >> 2);
+  r = a.commit(0); if (r) return r;
+  r = hop_launch_ssref_commit(c, n, a[dr], a[dy], a[dcb], a[dcr], 1); if (r) return r;
+  return a.sync();
 }
 
 int hop_ssref_commit_cus_device(hop_ctx* c, int n, const int32_t* d_rect4, const int16_t* d_rec_y, const int16_t* d_rec_cb, const int16_t* d_rec_cr) {
@@ -340,37 +475,22 @@ int hop_me_search_device(hop_ctx* c, int n, const hop_pu_job* d_jobs, hop_pu_res
   // separate streams: PUs are independent, the results do not depend on the cut.
   const int parts = (n >= 16384) ? c->lanes : 1;
   const int per = ((n + parts - 1) / parts + 4) / 5 * 5;
-  if (parts > 1) {
-    HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
-    for (int k = 0; k < parts - 1; k++) HIPCHK(c, hipStreamWaitEvent(c->xstream[k], c->ev_fork, 0));
-  }
-  int r = me_pipeline(c, std::min(per, n), d_jobs, d_results, stage); if (r) return r;
-  for (int k = 0; k < parts - 1; k++) {
-    const int o = (k + 1) * per, m = std::min(per, n - o);
-    if (m <= 0) break;
-    std::swap(c->stream, c->xstream[k]); std::swap(c->scratch, c->xscratch[k]); std::swap(c->scratch_bytes, c->xscratch_bytes[k]);
-    r = me_pipeline(c, m, d_jobs + o, d_results + o, stage);
-    hipError_t e = hipEventRecord(c->ev_join[k], c->stream);
-    std::swap(c->stream, c->xstream[k]); std::swap(c->scratch, c->xscratch[k]); std::swap(c->scratch_bytes, c->xscratch_bytes[k]);
-    if (r) return r;
-    if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, c->ev_join[k], 0);
-    if (e != hipSuccess) return hop_set_err(c, HOP_ERR_DEVICE, "hop_me_search_device: stream join: %s", hipGetErrorString(e));
-  }
-  return HOP_OK;
+  return run_on_lanes(c, parts, "hop_me_search_device", [&](int k) {
+    const int o = k * per, m = std::min(per, n - o);
+    return m > 0 ? me_pipeline(c, m, d_jobs + o, d_results + o, stage) : HOP_OK;
+  });
 }
 
 int hop_me_search(hop_ctx* c, int n, const hop_pu_job* jobs, hop_pu_result* results, int stage) {
   if (!c || n < 0 || (n && (!jobs || !results))) return hop_set_err(c, HOP_ERR_ARG, "hop_me_search: bad argument");
   if (n == 0) return HOP_OK;
   int r = hop_check_pu_jobs(c, n, jobs); if (r) return r;
-  size_t bj = (size_t)n * sizeof(hop_pu_job), o_r = (bj + 255) & ~(size_t)255, br = (size_t)n * sizeof(hop_pu_result);
-  void* st; r = hop_stage(c, o_r + br, &st); if (r) return r;
-  hop_pu_job* dj = (hop_pu_job*)st; hop_pu_result* dr = (hop_pu_result*)((char*)st + o_r);
-  HIPCHK(c, hipMemcpyAsync(dj, jobs, bj, hipMemcpyHostToDevice, c->stream));
-  r = hop_me_search_device(c, n, dj, dr, stage); if (r) return r;
-  HIPCHK(c, hipMemcpyAsync(results, dr, br, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return HOP_OK;
+  stage_arena a(c);
+  auto dj = a.in(jobs, n); auto dr = a.out<hop_pu_result>(n);
+  r = a.commit(0); if (r) return r;
+  r = hop_me_search_device(c, n, a[dj], a[dr], stage); if (r) return r;
+  r = a.download(results, dr); if (r) return r;
+  return a.sync();
 }
 
 int hop_pred_inter_device(hop_ctx* c, int n, const hop_pred_job* d_jobs) {
@@ -420,23 +540,18 @@ int hop_pred_inter(hop_ctx* c, int n, const hop_pred_job* jobs, int16_t* out_y, 
   std::vector<int64_t> offs(n);
   size_t tot = 0;
   for (int i = 0; i < n; i++) { offs[i] = (int64_t)tot; tot += (size_t)jobs[i].w * jobs[i].h; }
-  size_t bj = (size_t)n * sizeof(hop_pred_job), o_o = (bj + 255) & ~(size_t)255, bo = (size_t)n * 8;
-  size_t o_y = (o_o + bo + 255) & ~(size_t)255, o_cb = (o_y + tot * 2 + 255) & ~(size_t)255, o_cr = (o_cb + tot / 2 + 255) & ~(size_t)255;
-  void* st; int r = hop_stage(c, o_cr + tot / 2 + 256, &st); if (r) return r;
-  char* b = (char*)st;
-  HIPCHK(c, hipMemcpyAsync(b, jobs, bj, hipMemcpyHostToDevice, c->stream));
-  r = hop_launch_pred(c, n, (const hop_pred_job*)b); if (r) return r;
+  stage_arena a(c);
+  auto dj = a.in(jobs, n); auto d_off = a.out<int64_t>(n); auto dy = a.out<int16_t>(tot); auto dcb = a.out<int16_t>(tot / 4); auto dcr = a.out<int16_t>(tot / 4);
+  int r = a.commit(256); if (r) return r;
+  r = hop_launch_pred(c, n, a[dj]); if (r) return r;
   if (out_y && out_cb && out_cr) {
-    HIPCHK(c, hipMemcpyAsync(b + o_o, offs.data(), bo, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_gather_pred, dim3(n), dim3(256), 0, c->stream, (const hop_pred_job*)b, (const int64_t*)(b + o_o),
-                       c->pred[0], c->pred[1], c->pred[2], c->pic_w, (int16_t*)(b + o_y), (int16_t*)(b + o_cb), (int16_t*)(b + o_cr));
+    r = a.upload(d_off, offs.data()); if (r) return r;
+    hipLaunchKernelGGL(k_gather_pred, dim3(n), dim3(256), 0, c->stream, (const hop_pred_job*)a[dj], (const int64_t*)a[d_off],
+                       c->pred[0], c->pred[1], c->pred[2], c->pic_w, a[dy], a[dcb], a[dcr]);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(out_y, b + o_y, tot * 2, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out_cb, b + o_cb, tot / 2, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out_cr, b + o_cr, tot / 2, hipMemcpyDeviceToHost, c->stream));
+    if ((r = a.download(out_y, dy)) || (r = a.download(out_cb, dcb)) || (r = a.download(out_cr, dcr))) return r;
   }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return HOP_OK;
+  return a.sync();
 }
 
 int hop_pred_upload(hop_ctx* c, int comp, const int16_t* src) {
@@ -475,47 +590,30 @@ int hop_tu_roundtrip(hop_ctx* c, int n, const hop_tu_job* jobs, hop_tu_result* r
       return hop_set_err(c, HOP_ERR_ARG, "TU job %d: illegal transform unit", i);
     offs[i] = (int64_t)tot; tot += (size_t)N * N;
   }
-  const size_t bj = (size_t)n * sizeof(hop_tu_job), o_r = (bj + 255) & ~(size_t)255, o_o = (o_r + (size_t)n * sizeof(hop_tu_result) + 255) & ~(size_t)255;
-  const size_t o_l = (o_o + (size_t)n * 8 + 255) & ~(size_t)255;
-  void* st; int r = hop_stage(c, o_l + (levels_out ? tot * 4 : 0) + 256, &st); if (r) return r;
-  char* b = (char*)st;
-  HIPCHK(c, hipMemcpyAsync(b, jobs, bj, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(b + o_o, offs.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-  r = hop_launch_tu(c, n, (const hop_tu_job*)b, (hop_tu_result*)(b + o_r), levels_out ? (int32_t*)(b + o_l) : nullptr, (const int64_t*)(b + o_o));
-  if (r) return r;
-  HIPCHK(c, hipMemcpyAsync(results, b + o_r, (size_t)n * sizeof(hop_tu_result), hipMemcpyDeviceToHost, c->stream));
-  if (levels_out) HIPCHK(c, hipMemcpyAsync(levels_out, b + o_l, tot * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return HOP_OK;
+  stage_arena a(c);
+  auto dj = a.in(jobs, n); auto dr = a.out<hop_tu_result>(n); auto d_off = a.in(offs.data(), n); auto dl = a.out<int32_t>(levels_out ? tot : 0);
+  int r = a.commit(256); if (r) return r;
+  r = hop_launch_tu(c, n, a[dj], a[dr], levels_out ? a[dl] : nullptr, a[d_off]); if (r) return r;
+  r = a.download(results, dr); if (r) return r;
+  if (levels_out && (r = a.download(levels_out, dl))) return r;
+  return a.sync();
 }
 
 int hop_intra_rough(hop_ctx* c, int n, const hop_intra_job* jobs, uint32_t* satd_out) {
   if (!c || n < 0 || (n && (!jobs || !satd_out))) return hop_set_err(c, HOP_ERR_ARG, "hop_intra_rough: bad argument");
   if (!c->have_orig) return hop_set_err(c, HOP_ERR_STATE, "hop_intra_rough: hop_upload_orig has not been called");
   if (n == 0) return HOP_OK;
+  int u = 0;
   for (int i = 0; i < n; i++) {
-    const hop_intra_job& j = jobs[i];
-    const int N = j.size;
-    if (!(N == 4 || N == 8 || N == 16 || N == 32 || N == 64) || j.x < 0 || j.y < 0 || (j.x & 3) || (j.y & 3) || j.x + N > c->pic_w || j.y + N > c->pic_h)
-      return hop_set_err(c, HOP_ERR_ARG, "intra job %d: illegal block", i);
-    // an available unit must lie inside the picture (the reference derives availability from existing CUs)
-    const int U = N / 4;
-    for (int u = 0; u < 4 * U + 1; u++) if (j.flags[u]) {
-      bool ok;
-      if (u < 2 * U) ok = j.x > 0 && j.y + 4 * (2 * U - 1 - u) + 4 <= c->pic_h;
-      else if (u == 2 * U) ok = j.x > 0 && j.y > 0;
-      else ok = j.y > 0 && j.x + 4 * (u - 2 * U - 1) + 4 <= c->pic_w;
-      if (!ok) return hop_set_err(c, HOP_ERR_ARG, "intra job %d: neighbour unit %d flagged available but outside the picture", i, u);
-    }
+    if (!intra_block_ok(c, jobs[i], 0)) return hop_set_err(c, HOP_ERR_ARG, "intra job %d: illegal block", i);
+    if (!intra_neighbours_ok(c, jobs[i], 0, &u)) return hop_set_err(c, HOP_ERR_ARG, "intra job %d: neighbour unit %d flagged available but outside the picture", i, u);
   }
-  const size_t bj = (size_t)n * sizeof(hop_intra_job), o_o = (bj + 255) & ~(size_t)255;
-  void* st; int r = hop_stage(c, o_o + (size_t)n * 35 * 4, &st); if (r) return r;
-  char* b = (char*)st;
-  HIPCHK(c, hipMemcpyAsync(b, jobs, bj, hipMemcpyHostToDevice, c->stream));
-  r = hop_launch_intra(c, n, (const hop_intra_job*)b, (uint32_t*)(b + o_o)); if (r) return r;
-  HIPCHK(c, hipMemcpyAsync(satd_out, b + o_o, (size_t)n * 35 * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return HOP_OK;
+  stage_arena a(c);
+  auto dj = a.in(jobs, n); auto ds = a.out<uint32_t>((size_t)n * 35);
+  int r = a.commit(0); if (r) return r;
+  r = hop_launch_intra(c, n, a[dj], a[ds]); if (r) return r;
+  r = a.download(satd_out, ds); if (r) return r;
+  return a.sync();
 }
 
 int hop_tu_roundtrip_device(hop_ctx* c, int n, const hop_tu_job* d_jobs, hop_tu_result* d_results, int32_t* d_levels, const int64_t* d_level_offsets) {
@@ -551,21 +649,13 @@ int hop_rdoq(hop_ctx* c, int n, const hop_rdoq_job* jobs, int n_tables, const ho
         j.coeff_offset < 0 || (size_t)j.coeff_offset + n2 > n_coeff || j.estbits_index < 0 || j.estbits_index >= n_tables)
       return hop_set_err(c, HOP_ERR_ARG, "RDOQ job %d: illegal transform unit / table / offset", i);
   }
-  const size_t bj = (size_t)n * sizeof(hop_rdoq_job), o_t = (bj + 255) & ~(size_t)255, bt = (size_t)n_tables * sizeof(hop_estbits);
-  const size_t o_s = (o_t + bt + 255) & ~(size_t)255, o_d = (o_s + n_coeff * 4 + 255) & ~(size_t)255, o_a = (o_d + n_coeff * 4 + 255) & ~(size_t)255;
-  void* st; int r = hop_stage(c, o_a + (size_t)n * 4 + 256, &st); if (r) return r;
-  char* b = (char*)st;
-  HIPCHK(c, hipMemcpyAsync(b, jobs, bj, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(b + o_t, tables, bt, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(b + o_s, src, n_coeff * 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemsetAsync(b + o_d, 0, n_coeff * 4, c->stream));
+  stage_arena a(c);
+  auto dj = a.in(jobs, n); auto dt = a.in(tables, n_tables); auto ds = a.in(src, n_coeff); auto dd = a.zero<int32_t>(n_coeff); auto da = a.out<uint32_t>(n);
+  int r = a.commit(256); if (r) return r;
   void* work; r = hop_scratch(c, hop_rdoq_work_bytes(n), &work); if (r) return r;
-  r = hop_launch_rdoq(c, n, (const hop_rdoq_job*)b, (const hop_estbits*)(b + o_t), (const int32_t*)(b + o_s), (int32_t*)(b + o_d), (uint32_t*)(b + o_a), work);
-  if (r) return r;
-  HIPCHK(c, hipMemcpyAsync(dst, b + o_d, n_coeff * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(abs_sum, b + o_a, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return HOP_OK;
+  r = hop_launch_rdoq(c, n, a[dj], a[dt], a[ds], a[dd], a[da], work); if (r) return r;
+  if ((r = a.download(dst, dd)) || (r = a.download(abs_sum, da))) return r;
+  return a.sync();
 }
 
 int hop_coeff_bits_device(hop_ctx* c, int n, const hop_coeff_bits_job* d_jobs, const hop_cabac_ctx* d_ctx_in, const int32_t* d_coef,
@@ -585,21 +675,14 @@ int hop_coeff_bits(hop_ctx* c, int n, const hop_coeff_bits_job* jobs, int n_ctx,
         j.ctx_index < 0 || j.ctx_index >= n_ctx || j.coeff_offset < 0 || (size_t)j.coeff_offset + ((size_t)1 << (2 * j.log2_size)) > n_coeff)
       return hop_set_err(c, HOP_ERR_ARG, "coeff-bits job %d: illegal transform unit / context index / offset", i);
   }
-  for (int k = 0; k < n_ctx; k++) for (int i = 0; i < 150; i++) if (ctx_in[k].state[i] > 127) return hop_set_err(c, HOP_ERR_ARG, "context snapshot %d: state %d out of range", k, i);
-  const size_t bj = (size_t)n * sizeof(hop_coeff_bits_job), o_c = (bj + 255) & ~(size_t)255, bc = (size_t)n_ctx * sizeof(hop_cabac_ctx);
-  const size_t o_s = (o_c + bc + 255) & ~(size_t)255, o_b = (o_s + n_coeff * 4 + 255) & ~(size_t)255, o_o = (o_b + (size_t)n * 8 + 255) & ~(size_t)255;
-  void* st; int r = hop_stage(c, o_o + (ctx_out ? (size_t)n * sizeof(hop_cabac_ctx) : 0) + 256, &st); if (r) return r;
-  char* b = (char*)st;
-  HIPCHK(c, hipMemcpyAsync(b, jobs, bj, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(b + o_c, ctx_in, bc, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(b + o_s, coef, n_coeff * 4, hipMemcpyHostToDevice, c->stream));
-  r = hop_launch_coeff_bits(c, n, (const hop_coeff_bits_job*)b, (const hop_cabac_ctx*)(b + o_c), (const int32_t*)(b + o_s), (unsigned long long*)(b + o_b),
-                            ctx_out ? (hop_cabac_ctx*)(b + o_o) : nullptr);
-  if (r) return r;
-  HIPCHK(c, hipMemcpyAsync(bits, b + o_b, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-  if (ctx_out) HIPCHK(c, hipMemcpyAsync(ctx_out, b + o_o, (size_t)n * sizeof(hop_cabac_ctx), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return HOP_OK;
+  if (!ctx_states_ok(c, n_ctx, ctx_in, nullptr)) return HOP_ERR_ARG;
+  stage_arena a(c);
+  auto dj = a.in(jobs, n); auto dc = a.in(ctx_in, n_ctx); auto ds = a.in(coef, n_coeff); auto db = a.out<uint64_t>(n); auto dx = a.out<hop_cabac_ctx>(ctx_out ? n : 0);
+  int r = a.commit(256); if (r) return r;
+  r = hop_launch_coeff_bits(c, n, a[dj], a[dc], a[ds], (unsigned long long*)a[db], ctx_out ? a[dx] : nullptr); if (r) return r;
+  r = a.download(bits, db); if (r) return r;
+  if (ctx_out && (r = a.download(ctx_out, dx))) return r;
+  return a.sync();
 }
 
 int hop_tu_rd_device(hop_ctx* c, int n, const hop_tu_rd_job* d_jobs, const hop_cabac_ctx* d_ctx_in, const int64_t* d_coef_offsets, size_t n_coeff,
@@ -626,34 +709,21 @@ int hop_intra_modes(hop_ctx* c, int n, const hop_intra_modes_job* jobs, const ui
     for (int k = 0; k < j.pred_num && ok; k++) ok = j.preds[k] >= 0 && j.preds[k] < 35;
     if (!ok) return hop_set_err(c, HOP_ERR_ARG, "intra modes job %d: illegal predictors / list size / context", i);
   }
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t o_s = al((size_t)n * sizeof(hop_intra_modes_job)), o_r = al(o_s + (size_t)n * 35 * 4);
-  void* st; int r = hop_stage(c, o_r + (size_t)n * sizeof(hop_intra_modes_result) + 256, &st); if (r) return r;
-  char* b = (char*)st;
-  HIPCHK(c, hipMemcpyAsync(b, jobs, (size_t)n * sizeof(hop_intra_modes_job), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(b + o_s, satd, (size_t)n * 35 * 4, hipMemcpyHostToDevice, c->stream));
-  r = hop_launch_intra_modes(c, n, (const hop_intra_modes_job*)b, (const uint32_t*)(b + o_s), (hop_intra_modes_result*)(b + o_r)); if (r) return r;
-  HIPCHK(c, hipMemcpyAsync(results, b + o_r, (size_t)n * sizeof(hop_intra_modes_result), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return HOP_OK;
+  stage_arena a(c);
+  auto dj = a.in(jobs, n); auto ds = a.in(satd, (size_t)n * 35); auto dr = a.out<hop_intra_modes_result>(n);
+  int r = a.commit(256); if (r) return r;
+  r = hop_launch_intra_modes(c, n, a[dj], a[ds], a[dr]); if (r) return r;
+  r = a.download(results, dr); if (r) return r;
+  return a.sync();
 }
 
 int hop_rqt_device(hop_ctx* c, int n, const hop_rqt_job* d_jobs, const hop_rqt_job* cls, const hop_cabac_ctx* d_ctx_in, hop_rqt_result* d_results, int32_t* d_coef_out,
                    hop_cabac_ctx* d_ctx_out) {
   if (!c || n < 0 || !cls || (n && (!d_jobs || !d_ctx_in || !d_results))) return hop_set_err(c, HOP_ERR_ARG, "hop_rqt_device: bad argument");
   if (!c->have_orig) return hop_set_err(c, HOP_ERR_STATE, "hop_rqt: hop_upload_orig has not been called");
-  if (cls->log2_cu < 3 || cls->log2_cu > 6 || cls->log2_max_tu < 2 || cls->log2_max_tu > 5 || cls->log2_min_tu_in_cu < 2 || cls->log2_min_tu_in_cu > cls->log2_max_tu ||
-      cls->log2_cu - cls->log2_min_tu_in_cu > 3 || cls->log2_cu - cls->log2_max_tu > 1) return hop_set_err(c, HOP_ERR_ARG, "hop_rqt_device: illegal CU class");
+  if (!rqt_class_ok(*cls)) return hop_set_err(c, HOP_ERR_ARG, "hop_rqt_device: illegal CU class");
   if (n == 0) return HOP_OK;
-  const size_t wb = hop_rqt_work_bytes(cls->log2_cu, n);
-  if (wb > c->rqt_bytes) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->rqt_buf) HIPCHK(c, hipFree(c->rqt_buf));
-    c->rqt_buf = nullptr; c->rqt_bytes = 0;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMalloc(&c->rqt_buf, wb + wb / 8));
-    c->rqt_bytes = wb + wb / 8;
-  }
+  int r = rqt_reserve(c, hop_rqt_work_bytes(cls->log2_cu, n)); if (r) return r;
   return hop_launch_rqt_class(c, cls->log2_cu, cls->log2_max_tu, cls->log2_min_tu_in_cu, cls->inter_split_flag ? 1 : 0, cls->sign_hide ? 1 : 0, cls->use_ts ? 1 : 0, n, d_jobs,
                               d_ctx_in, d_results, d_coef_out, d_ctx_out, c->rqt_buf, c->rqt_bytes);
 }
@@ -663,29 +733,9 @@ int hop_rqt_device_classes(hop_ctx* c, int n_classes, const int* n, const hop_rq
   if (!c || n_classes < 0 || (n_classes && (!n || !d_jobs || !cls || !d_results))) return hop_set_err(c, HOP_ERR_ARG, "hop_rqt_device_classes: bad argument");
   if (n_classes == 0) return HOP_OK;
   // classes are independent chains of small kernels: each runs on its own stream (with its own scratch and state buffers)
-  const int n_fork = std::min(n_classes, HOP_MAX_LANES) - 1;            // only the lanes this call uses (see hop_inter_cu_device_classes)
-  if (n_fork > 0) HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
-  for (int k = 0; k < n_fork; k++) HIPCHK(c, hipStreamWaitEvent(c->xstream[k], c->ev_fork, 0));
-  bool used[HOP_MAX_LANES - 1] = { false, false, false };
-  int rc = HOP_OK;
-  for (int i = 0; i < n_classes && rc == HOP_OK; i++) {
-    const int lane = i % HOP_MAX_LANES;
-    if (lane == 0) { rc = hop_rqt_device(c, n[i], d_jobs[i], cls + i, d_ctx_in, d_results[i], d_coef_out ? d_coef_out[i] : nullptr, d_ctx_out ? d_ctx_out[i] : nullptr); continue; }
-    const int k = lane - 1;
-    std::swap(c->stream, c->xstream[k]); std::swap(c->scratch, c->xscratch[k]); std::swap(c->scratch_bytes, c->xscratch_bytes[k]);
-    std::swap(c->rqt_buf, c->xrqt_buf[k]); std::swap(c->rqt_bytes, c->xrqt_bytes[k]); std::swap(c->walk_buf, c->xwalk_buf[k]); std::swap(c->walk_bytes, c->xwalk_bytes[k]);
-    rc = hop_rqt_device(c, n[i], d_jobs[i], cls + i, d_ctx_in, d_results[i], d_coef_out ? d_coef_out[i] : nullptr, d_ctx_out ? d_ctx_out[i] : nullptr);
-    std::swap(c->stream, c->xstream[k]); std::swap(c->scratch, c->xscratch[k]); std::swap(c->scratch_bytes, c->xscratch_bytes[k]);
-    std::swap(c->rqt_buf, c->xrqt_buf[k]); std::swap(c->rqt_bytes, c->xrqt_bytes[k]); std::swap(c->walk_buf, c->xwalk_buf[k]); std::swap(c->walk_bytes, c->xwalk_bytes[k]);
-    used[k] = true;
-  }
-  for (int k = 0; k < HOP_MAX_LANES - 1; k++) {
-    if (!used[k]) continue;
-    hipError_t e = hipEventRecord(c->ev_join[k], c->xstream[k]);
-    if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, c->ev_join[k], 0);
-    if (e != hipSuccess && rc == HOP_OK) rc = hop_set_err(c, HOP_ERR_DEVICE, "hop_rqt_device_classes: stream join: %s", hipGetErrorString(e));
-  }
-  return rc;
+  return run_on_lanes(c, n_classes, "hop_rqt_device_classes", [&](int i) {
+    return hop_rqt_device(c, n[i], d_jobs[i], cls + i, d_ctx_in, d_results[i], d_coef_out ? d_coef_out[i] : nullptr, d_ctx_out ? d_ctx_out[i] : nullptr);
+  });
 }
 
 int hop_rqt(hop_ctx* c, int n, const hop_rqt_job* jobs, int n_ctx, const hop_cabac_ctx* ctx_in, hop_rqt_result* results, int32_t* coef_out, hop_cabac_ctx* ctx_out) {
@@ -695,67 +745,39 @@ int hop_rqt(hop_ctx* c, int n, const hop_rqt_job* jobs, int n_ctx, const hop_cab
   std::vector<size_t> coff(n + 1, 0);
   for (int i = 0; i < n; i++) {
     const hop_rqt_job& j = jobs[i];
-    const int S = 1 << j.log2_cu;
-    bool ok = j.log2_cu >= 3 && j.log2_cu <= 6 && j.x >= 0 && j.y >= 0 && (j.x & (S - 1)) == 0 && (j.y & (S - 1)) == 0 && j.x + S <= c->pic_w && j.y + S <= c->pic_h &&
-              j.ctx_index >= 0 && j.ctx_index < n_ctx && j.log2_max_tu >= 2 && j.log2_max_tu <= 5 && j.log2_min_tu_in_cu >= 2 && j.log2_min_tu_in_cu <= j.log2_max_tu &&
-              j.log2_cu - j.log2_min_tu_in_cu <= 3 && j.log2_cu - j.log2_max_tu <= 1 && j.lambda_rd > 0.0;
+    bool ok = rqt_class_ok(j) && cu_rect_ok(c, j) && j.ctx_index >= 0 && j.ctx_index < n_ctx && j.lambda_rd > 0.0;
     for (int k = 0; k < 3 && ok; k++) ok = j.qp_scaled[k] >= 0 && j.qp_scaled[k] <= 87 && j.lambda_rdoq[k] > 0.0;
     if (!ok) return hop_set_err(c, HOP_ERR_ARG, "RQT job %d: illegal CU / transform-tree limits / snapshot / parameters", i);
-    coff[i + 1] = coff[i] + (size_t)S * S * 3 / 2;
+    coff[i + 1] = coff[i] + cu_coeffs(j.log2_cu);
   }
-  for (int k = 0; k < n_ctx; k++) for (int i = 0; i < 150; i++) if (ctx_in[k].state[i] > 127) return hop_set_err(c, HOP_ERR_ARG, "context snapshot %d: state %d out of range", k, i);
+  if (!ctx_states_ok(c, n_ctx, ctx_in, nullptr)) return HOP_ERR_ARG;
   // one pass per class of CUs (same size and transform-tree limits): the walk over the tree is the same for all of them
-  std::vector<char> done(n, 0);
-  for (int first = 0; first < n; first++) {
-    if (done[first]) continue;
-    const hop_rqt_job& f = jobs[first];
-    std::vector<int> idx; std::vector<hop_rqt_job> cls;
-    for (int i = first; i < n; i++) {
-      const hop_rqt_job& j = jobs[i];
-      if (!done[i] && j.log2_cu == f.log2_cu && j.log2_max_tu == f.log2_max_tu && j.log2_min_tu_in_cu == f.log2_min_tu_in_cu && !j.inter_split_flag == !f.inter_split_flag &&
-          !j.sign_hide == !f.sign_hide && !j.use_ts == !f.use_ts) { done[i] = 1; idx.push_back(i); cls.push_back(j); }
-    }
-    const int m = (int)idx.size();
-    const size_t cu3 = ((size_t)3 << (2 * f.log2_cu)) / 2;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_j = 0, o_c = al((size_t)m * sizeof(hop_rqt_job)), o_r = al(o_c + (size_t)n_ctx * sizeof(hop_cabac_ctx)), o_o = al(o_r + (size_t)m * sizeof(hop_rqt_result));
-    const size_t o_x = al(o_o + (size_t)m * cu3 * 4), o_w = al(o_x + (size_t)m * sizeof(hop_cabac_ctx));
-    void* st; int r = hop_stage(c, o_w + 256, &st); if (r) return r;
-    char* b = (char*)st;
-    HIPCHK(c, hipMemcpyAsync(b + o_j, cls.data(), (size_t)m * sizeof(hop_rqt_job), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b + o_c, ctx_in, (size_t)n_ctx * sizeof(hop_cabac_ctx), hipMemcpyHostToDevice, c->stream));
-    r = hop_rqt_device(c, m, (const hop_rqt_job*)(b + o_j), &f, (const hop_cabac_ctx*)(b + o_c), (hop_rqt_result*)(b + o_r), (int32_t*)(b + o_o), (hop_cabac_ctx*)(b + o_x));
-    if (r) return r;
-    std::vector<hop_rqt_result> rr(m); std::vector<int32_t> co((size_t)m * cu3); std::vector<hop_cabac_ctx> cx(m);
-    HIPCHK(c, hipMemcpyAsync(rr.data(), b + o_r, (size_t)m * sizeof(hop_rqt_result), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(co.data(), b + o_o, (size_t)m * cu3 * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(cx.data(), b + o_x, (size_t)m * sizeof(hop_cabac_ctx), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int t = 0; t < m; t++) {
-      results[idx[t]] = rr[t];
-      if (coef_out) memcpy(coef_out + coff[idx[t]], co.data() + (size_t)t * cu3, cu3 * 4);
-      if (ctx_out) ctx_out[idx[t]] = cx[t];
-    }
-  }
-  return HOP_OK;
+  auto same = [&](int p, int q) { return same_tree(jobs[p], jobs[q]) && !jobs[p].inter_split_flag == !jobs[q].inter_split_flag && !jobs[p].sign_hide == !jobs[q].sign_hide; };
+  return for_each_class(n, same, [&](const std::vector<int>& idx) {
+    const hop_rqt_job& f = jobs[idx[0]];
+    const size_t m = idx.size(), cu3 = cu_coeffs(f.log2_cu);
+    const std::vector<hop_rqt_job> cls = gather(jobs, idx);
+    stage_arena a(c);
+    auto dj = a.in(cls.data(), m); auto dc = a.in(ctx_in, n_ctx); auto dr = a.out<hop_rqt_result>(m); auto d_co = a.out<int32_t>(m * cu3); auto dx = a.out<hop_cabac_ctx>(m);
+    a.end_mark();
+    int r = a.commit(256); if (r) return r;
+    r = hop_rqt_device(c, (int)m, a[dj], &f, a[dc], a[dr], a[d_co], a[dx]); if (r) return r;
+    std::vector<hop_rqt_result> rr(m); std::vector<int32_t> co(m * cu3); std::vector<hop_cabac_ctx> cx(m);
+    if ((r = a.download(rr.data(), dr)) || (r = a.download(co.data(), d_co)) || (r = a.download(cx.data(), dx)) || (r = a.sync())) return r;
+    scatter(results, idx, rr.data());
+    if (coef_out) scatter(coef_out, idx, co.data(), cu3, coff.data());
+    if (ctx_out) scatter(ctx_out, idx, cx.data());
+    return (int)HOP_OK;
+  });
 }
 
 int hop_rqt_finish_device(hop_ctx* c, int n, const hop_rqt_job* d_jobs, const hop_rqt_job* cls, hop_rqt_result* d_results, int32_t* d_coef, const hop_cabac_ctx* d_ctx_after,
                           hop_cu_final* d_finals) {
   if (!c || n < 0 || !cls || (n && (!d_jobs || !d_results || !d_coef || !d_ctx_after || !d_finals))) return hop_set_err(c, HOP_ERR_ARG, "hop_rqt_finish_device: bad argument");
   if (!c->have_orig) return hop_set_err(c, HOP_ERR_STATE, "hop_rqt_finish: hop_upload_orig has not been called");
-  if (cls->log2_cu < 3 || cls->log2_cu > 6 || cls->log2_max_tu < 2 || cls->log2_max_tu > 5 || cls->log2_min_tu_in_cu < 2 || cls->log2_min_tu_in_cu > cls->log2_max_tu ||
-      cls->log2_cu - cls->log2_min_tu_in_cu > 3 || cls->log2_cu - cls->log2_max_tu > 1) return hop_set_err(c, HOP_ERR_ARG, "hop_rqt_finish_device: illegal CU class");
+  if (!rqt_class_ok(*cls)) return hop_set_err(c, HOP_ERR_ARG, "hop_rqt_finish_device: illegal CU class");
   if (n == 0) return HOP_OK;
-  const size_t wb = hop_rqt_finish_work_bytes(cls->log2_cu, cls->log2_max_tu, cls->log2_min_tu_in_cu, n);
-  if (wb > c->rqt_bytes) {                                         // the quadtree's state buffer is free again once its kernels are queued (same stream)
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->rqt_buf) HIPCHK(c, hipFree(c->rqt_buf));
-    c->rqt_buf = nullptr; c->rqt_bytes = 0;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMalloc(&c->rqt_buf, wb + wb / 8));
-    c->rqt_bytes = wb + wb / 8;
-  }
+  int r = rqt_reserve(c, hop_rqt_finish_work_bytes(cls->log2_cu, cls->log2_max_tu, cls->log2_min_tu_in_cu, n)); if (r) return r;
   return hop_launch_rqt_finish(c, cls->log2_cu, cls->log2_max_tu, cls->log2_min_tu_in_cu, cls->use_ts ? 1 : 0, n, d_jobs, d_results, d_coef, d_ctx_after, d_finals, c->rqt_buf);
 }
 
@@ -766,48 +788,24 @@ int hop_rqt_finish(hop_ctx* c, int n, const hop_rqt_job* jobs, hop_rqt_result* r
   std::vector<size_t> coff(n + 1, 0);
   for (int i = 0; i < n; i++) {
     const hop_rqt_job& j = jobs[i];
-    const int S = 1 << j.log2_cu;
-    const bool ok = j.log2_cu >= 3 && j.log2_cu <= 6 && j.x >= 0 && j.y >= 0 && (j.x & (S - 1)) == 0 && (j.y & (S - 1)) == 0 && j.x + S <= c->pic_w && j.y + S <= c->pic_h &&
-                    j.log2_max_tu >= 2 && j.log2_max_tu <= 5 && j.log2_min_tu_in_cu >= 2 && j.log2_min_tu_in_cu <= j.log2_max_tu && j.log2_cu - j.log2_min_tu_in_cu <= 3 &&
-                    j.log2_cu - j.log2_max_tu <= 1 && j.lambda_rd > 0.0;
-    if (!ok) return hop_set_err(c, HOP_ERR_ARG, "RQT finish job %d: illegal CU / transform-tree limits / parameters", i);
-    coff[i + 1] = coff[i] + (size_t)S * S * 3 / 2;
+    if (!(rqt_class_ok(j) && cu_rect_ok(c, j) && j.lambda_rd > 0.0)) return hop_set_err(c, HOP_ERR_ARG, "RQT finish job %d: illegal CU / transform-tree limits / parameters", i);
+    coff[i + 1] = coff[i] + cu_coeffs(j.log2_cu);
   }
-  std::vector<char> done(n, 0);
-  for (int first = 0; first < n; first++) {
-    if (done[first]) continue;
-    const hop_rqt_job& f = jobs[first];
-    std::vector<int> idx; std::vector<hop_rqt_job> cls; std::vector<hop_rqt_result> rr; std::vector<hop_cabac_ctx> cx;
-    for (int i = first; i < n; i++) {
-      const hop_rqt_job& j = jobs[i];
-      if (!done[i] && j.log2_cu == f.log2_cu && j.log2_max_tu == f.log2_max_tu && j.log2_min_tu_in_cu == f.log2_min_tu_in_cu && !j.use_ts == !f.use_ts) {
-        done[i] = 1; idx.push_back(i); cls.push_back(j); rr.push_back(results[i]); cx.push_back(ctx_after[i]);
-      }
-    }
-    const int m = (int)idx.size();
-    const size_t cu3 = ((size_t)3 << (2 * f.log2_cu)) / 2;
-    std::vector<int32_t> co((size_t)m * cu3);
-    for (int t = 0; t < m; t++) memcpy(co.data() + (size_t)t * cu3, coef + coff[idx[t]], cu3 * 4);
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_j = 0, o_r = al((size_t)m * sizeof(hop_rqt_job)), o_o = al(o_r + (size_t)m * sizeof(hop_rqt_result)), o_x = al(o_o + (size_t)m * cu3 * 4);
-    const size_t o_f = al(o_x + (size_t)m * sizeof(hop_cabac_ctx)), o_w = al(o_f + (size_t)m * sizeof(hop_cu_final));
-    void* st; int r = hop_stage(c, o_w + hop_rqt_finish_work_bytes(f.log2_cu, f.log2_max_tu, f.log2_min_tu_in_cu, m) + 256, &st); if (r) return r;
-    char* b = (char*)st;
-    HIPCHK(c, hipMemcpyAsync(b + o_j, cls.data(), (size_t)m * sizeof(hop_rqt_job), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b + o_r, rr.data(), (size_t)m * sizeof(hop_rqt_result), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b + o_o, co.data(), (size_t)m * cu3 * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b + o_x, cx.data(), (size_t)m * sizeof(hop_cabac_ctx), hipMemcpyHostToDevice, c->stream));
-    r = hop_launch_rqt_finish(c, f.log2_cu, f.log2_max_tu, f.log2_min_tu_in_cu, f.use_ts ? 1 : 0, m, (const hop_rqt_job*)(b + o_j), (hop_rqt_result*)(b + o_r), (int32_t*)(b + o_o),
-                              (const hop_cabac_ctx*)(b + o_x), (hop_cu_final*)(b + o_f), b + o_w);
-    if (r) return r;
+  return for_each_class(n, [&](int p, int q) { return same_tree(jobs[p], jobs[q]); }, [&](const std::vector<int>& idx) {
+    const hop_rqt_job& f = jobs[idx[0]];
+    const size_t m = idx.size(), cu3 = cu_coeffs(f.log2_cu);
+    const std::vector<hop_rqt_job> cls = gather(jobs, idx); const std::vector<hop_cabac_ctx> cx = gather(ctx_after, idx);
+    std::vector<hop_rqt_result> rr = gather(results, idx); std::vector<int32_t> co = gather(coef, idx, cu3, coff.data());
+    stage_arena a(c);                                                  // the kernel's work area is the tail of the same reservation
+    auto dj = a.in(cls.data(), m); auto dr = a.in(rr.data(), m); auto d_co = a.in(co.data(), m * cu3); auto dx = a.in(cx.data(), m); auto df = a.out<hop_cu_final>(m);
+    auto dw = a.out<char>(hop_rqt_finish_work_bytes(f.log2_cu, f.log2_max_tu, f.log2_min_tu_in_cu, (int)m));
+    int r = a.commit(256); if (r) return r;
+    r = hop_launch_rqt_finish(c, f.log2_cu, f.log2_max_tu, f.log2_min_tu_in_cu, f.use_ts ? 1 : 0, (int)m, a[dj], a[dr], a[d_co], a[dx], a[df], a[dw]); if (r) return r;
     std::vector<hop_cu_final> ff(m);
-    HIPCHK(c, hipMemcpyAsync(rr.data(), b + o_r, (size_t)m * sizeof(hop_rqt_result), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(co.data(), b + o_o, (size_t)m * cu3 * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(ff.data(), b + o_f, (size_t)m * sizeof(hop_cu_final), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int t = 0; t < m; t++) { results[idx[t]] = rr[t]; finals[idx[t]] = ff[t]; memcpy(coef + coff[idx[t]], co.data() + (size_t)t * cu3, cu3 * 4); }
-  }
-  return HOP_OK;
+    if ((r = a.download(rr.data(), dr)) || (r = a.download(co.data(), d_co)) || (r = a.download(ff.data(), df)) || (r = a.sync())) return r;
+    scatter(results, idx, rr.data()); scatter(finals, idx, ff.data()); scatter(coef, idx, co.data(), cu3, coff.data());
+    return (int)HOP_OK;
+  });
 }
 
 int hop_intra_cu_bits(hop_ctx* c, int n, const hop_rqt_job* jobs, const hop_intra_cu_syntax* syntax, const hop_rqt_result* results, const int32_t* coef, int n_ctx,
@@ -818,56 +816,32 @@ int hop_intra_cu_bits(hop_ctx* c, int n, const hop_rqt_job* jobs, const hop_intr
   for (int i = 0; i < n; i++) {
     const hop_rqt_job& j = jobs[i]; const hop_intra_cu_syntax& y = syntax[i];
     const int parts = 1 << (2 * (j.log2_cu - 2));
-    bool ok = j.log2_cu >= 3 && j.log2_cu <= 6 && j.ctx_index >= 0 && j.ctx_index < n_ctx && j.log2_max_tu >= 2 && j.log2_max_tu <= 5 && j.log2_min_tu_in_cu >= 2 &&
-              j.log2_min_tu_in_cu <= j.log2_max_tu && j.log2_cu - j.log2_min_tu_in_cu <= 3 && j.log2_cu - j.log2_max_tu <= 1 && y.skip_ctx >= 0 && y.skip_ctx <= 2 &&
+    bool ok = rqt_class_ok(j) && j.ctx_index >= 0 && j.ctx_index < n_ctx && y.skip_ctx >= 0 && y.skip_ctx <= 2 &&
               y.tr_depth >= 0 && y.tr_depth <= 3 && y.part >= 0 && y.part < parts && (y.part % (parts >> (2 * y.tr_depth))) == 0 && (y.b_luma || y.b_chroma);
     for (int p = 0; p < (y.part_nxn ? 4 : 1) && ok; p++) ok = y.luma_dir[p] >= 0 && y.luma_dir[p] < 35 && y.pred_num[p] >= 0 && y.pred_num[p] <= 3;
     if (!ok) return hop_set_err(c, HOP_ERR_ARG, "intra CU bits job %d: illegal CU class / node / syntax elements / snapshot", i);
-    coff[i + 1] = coff[i] + (((size_t)3 << (2 * j.log2_cu)) >> 1);
+    coff[i + 1] = coff[i] + cu_coeffs(j.log2_cu);
   }
-  for (int k = 0; k < n_ctx; k++) {
-    for (int i = 0; i < 150; i++) if (ctx_in[k].state[i] > 127) return hop_set_err(c, HOP_ERR_ARG, "context snapshot %d: state %d out of range", k, i);
-    for (int i = 0; i < 19; i++) if (cu_ctx_in[k].state[i] > 127) return hop_set_err(c, HOP_ERR_ARG, "CU context snapshot %d: state %d out of range", k, i);
-  }
-  std::vector<char> done(n, 0);
-  for (int first = 0; first < n; first++) {
-    if (done[first]) continue;
-    const hop_rqt_job& f = jobs[first];
-    std::vector<int> idx; std::vector<hop_rqt_job> cls; std::vector<hop_intra_cu_syntax> sy; std::vector<hop_rqt_result> rr;
-    for (int i = first; i < n; i++) {
-      const hop_rqt_job& j = jobs[i];
-      if (!done[i] && j.log2_cu == f.log2_cu && j.log2_max_tu == f.log2_max_tu && j.log2_min_tu_in_cu == f.log2_min_tu_in_cu && !j.sign_hide == !f.sign_hide && !j.use_ts == !f.use_ts) {
-        done[i] = 1; idx.push_back(i); cls.push_back(j); sy.push_back(syntax[i]); rr.push_back(results[i]);
-      }
-    }
-    const int m = (int)idx.size();
-    const size_t cu3 = ((size_t)3 << (2 * f.log2_cu)) / 2;
-    std::vector<int32_t> co((size_t)m * cu3);
-    for (int t = 0; t < m; t++) memcpy(co.data() + (size_t)t * cu3, coef + coff[idx[t]], cu3 * 4);
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_j = 0, o_y = al((size_t)m * sizeof(hop_rqt_job)), o_r = al(o_y + (size_t)m * sizeof(hop_intra_cu_syntax)), o_o = al(o_r + (size_t)m * sizeof(hop_rqt_result));
-    const size_t o_c = al(o_o + (size_t)m * cu3 * 4), o_u = al(o_c + (size_t)n_ctx * sizeof(hop_cabac_ctx)), o_b = al(o_u + (size_t)n_ctx * sizeof(hop_cabac_cu_ctx));
-    const size_t o_x = al(o_b + (size_t)m * 4), o_v = al(o_x + (size_t)m * sizeof(hop_cabac_ctx)), o_e = al(o_v + (size_t)m * sizeof(hop_cabac_cu_ctx));
-    void* st; int r = hop_stage(c, o_e + 256, &st); if (r) return r;
-    char* b = (char*)st;
-    HIPCHK(c, hipMemcpyAsync(b + o_j, cls.data(), (size_t)m * sizeof(hop_rqt_job), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b + o_y, sy.data(), (size_t)m * sizeof(hop_intra_cu_syntax), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b + o_r, rr.data(), (size_t)m * sizeof(hop_rqt_result), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b + o_o, co.data(), (size_t)m * cu3 * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b + o_c, ctx_in, (size_t)n_ctx * sizeof(hop_cabac_ctx), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b + o_u, cu_ctx_in, (size_t)n_ctx * sizeof(hop_cabac_cu_ctx), hipMemcpyHostToDevice, c->stream));
-    r = hop_launch_intra_cu_bits(c, f.log2_cu, f.log2_max_tu, f.log2_min_tu_in_cu, f.sign_hide ? 1 : 0, f.use_ts ? 1 : 0, m, (const hop_rqt_job*)(b + o_j), (const hop_intra_cu_syntax*)(b + o_y),
-                                 (const hop_rqt_result*)(b + o_r), (const int32_t*)(b + o_o), (const hop_cabac_ctx*)(b + o_c), (const hop_cabac_cu_ctx*)(b + o_u), (uint32_t*)(b + o_b),
-                                 (hop_cabac_ctx*)(b + o_x), (hop_cabac_cu_ctx*)(b + o_v));
+  if (!ctx_states_ok(c, n_ctx, ctx_in, cu_ctx_in)) return HOP_ERR_ARG;
+  return for_each_class(n, [&](int p, int q) { return same_tree(jobs[p], jobs[q]) && !jobs[p].sign_hide == !jobs[q].sign_hide; }, [&](const std::vector<int>& idx) {
+    const hop_rqt_job& f = jobs[idx[0]];
+    const size_t m = idx.size(), cu3 = cu_coeffs(f.log2_cu);
+    const std::vector<hop_rqt_job> cls = gather(jobs, idx); const std::vector<hop_intra_cu_syntax> sy = gather(syntax, idx);
+    const std::vector<hop_rqt_result> rr = gather(results, idx); const std::vector<int32_t> co = gather(coef, idx, cu3, coff.data());
+    stage_arena a(c);
+    auto dj = a.in(cls.data(), m); auto dy = a.in(sy.data(), m); auto dr = a.in(rr.data(), m); auto d_co = a.in(co.data(), m * cu3); auto dc = a.in(ctx_in, n_ctx); auto du = a.in(cu_ctx_in, n_ctx);
+    auto db = a.out<uint32_t>(m); auto dx = a.out<hop_cabac_ctx>(m); auto dv = a.out<hop_cabac_cu_ctx>(m);
+    a.end_mark();
+    int r = a.commit(256); if (r) return r;
+    r = hop_launch_intra_cu_bits(c, f.log2_cu, f.log2_max_tu, f.log2_min_tu_in_cu, f.sign_hide ? 1 : 0, f.use_ts ? 1 : 0, (int)m, a[dj], a[dy], a[dr], a[d_co], a[dc], a[du], a[db], a[dx], a[dv]);
     if (r) return r;
     std::vector<uint32_t> bb(m); std::vector<hop_cabac_ctx> cx(m); std::vector<hop_cabac_cu_ctx> cv(m);
-    HIPCHK(c, hipMemcpyAsync(bb.data(), b + o_b, (size_t)m * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(cx.data(), b + o_x, (size_t)m * sizeof(hop_cabac_ctx), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(cv.data(), b + o_v, (size_t)m * sizeof(hop_cabac_cu_ctx), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int t = 0; t < m; t++) { bits[idx[t]] = bb[t]; if (ctx_out) ctx_out[idx[t]] = cx[t]; if (cu_ctx_out) cu_ctx_out[idx[t]] = cv[t]; }
-  }
-  return HOP_OK;
+    if ((r = a.download(bb.data(), db)) || (r = a.download(cx.data(), dx)) || (r = a.download(cv.data(), dv)) || (r = a.sync())) return r;
+    scatter(bits, idx, bb.data());
+    if (ctx_out) scatter(ctx_out, idx, cx.data());
+    if (cu_ctx_out) scatter(cu_ctx_out, idx, cv.data());
+    return (int)HOP_OK;
+  });
 }
 
 int hop_intra_rqt_device(hop_ctx* c, int n, const hop_rqt_job* d_jobs, const hop_rqt_job* cls, int tr_depth, int check_first, const hop_intra_cu_syntax* d_syntax,
@@ -875,19 +849,10 @@ int hop_intra_rqt_device(hop_ctx* c, int n, const hop_rqt_job* d_jobs, const hop
                          hop_cabac_ctx* d_ctx_out, hop_cabac_cu_ctx* d_cu_ctx_out) {
   if (!c || n < 0 || !cls || (n && (!d_jobs || !d_syntax || !d_opts || !d_ctx_in || !d_cu_ctx_in || !d_results))) return hop_set_err(c, HOP_ERR_ARG, "hop_intra_rqt_device: bad argument");
   if (!c->have_orig) return hop_set_err(c, HOP_ERR_STATE, "hop_intra_rqt: hop_upload_orig has not been called");
-  if (cls->log2_cu < 3 || cls->log2_cu > 6 || cls->log2_max_tu < 2 || cls->log2_max_tu > 5 || cls->log2_min_tu_in_cu < 2 || cls->log2_min_tu_in_cu > cls->log2_max_tu ||
-      cls->log2_cu - cls->log2_min_tu_in_cu > 3 || cls->log2_cu - cls->log2_max_tu > 1 || tr_depth < 0 || tr_depth > 1 || cls->log2_cu - tr_depth < cls->log2_min_tu_in_cu)
+  if (!rqt_class_ok(*cls) || tr_depth < 0 || tr_depth > 1 || cls->log2_cu - tr_depth < cls->log2_min_tu_in_cu)
     return hop_set_err(c, HOP_ERR_ARG, "hop_intra_rqt_device: illegal PU class");
   if (n == 0) return HOP_OK;
-  const size_t wb = hop_intra_rqt_work_bytes(cls->log2_cu, n);
-  if (wb > c->rqt_bytes) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->rqt_buf) HIPCHK(c, hipFree(c->rqt_buf));
-    c->rqt_buf = nullptr; c->rqt_bytes = 0;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMalloc(&c->rqt_buf, wb + wb / 8));
-    c->rqt_bytes = wb + wb / 8;
-  }
+  int r = rqt_reserve(c, hop_intra_rqt_work_bytes(cls->log2_cu, n)); if (r) return r;
   return hop_launch_intra_rqt(c, cls->log2_cu, cls->log2_max_tu, cls->log2_min_tu_in_cu, cls->sign_hide ? 1 : 0, cls->use_ts ? 1 : 0, tr_depth, check_first ? 1 : 0, n, d_jobs, d_syntax,
                               d_opts, d_ctx_in, d_cu_ctx_in, d_results, d_coef_out, d_ctx_out, d_cu_ctx_out, c->rqt_buf, c->rqt_bytes, nullptr);
 }
@@ -900,61 +865,36 @@ int hop_intra_rqt(hop_ctx* c, int n, const hop_rqt_job* jobs, const hop_intra_cu
   std::vector<size_t> coff(n + 1, 0);
   for (int i = 0; i < n; i++) {
     const hop_rqt_job& j = jobs[i]; const hop_intra_cu_syntax& y = syntax[i];
-    const int S = 1 << j.log2_cu, parts = 1 << (2 * (j.log2_cu - 2));
-    bool ok = j.log2_cu >= 3 && j.log2_cu <= 6 && j.x >= 0 && j.y >= 0 && (j.x & (S - 1)) == 0 && (j.y & (S - 1)) == 0 && j.x + S <= c->pic_w && j.y + S <= c->pic_h &&
-              j.ctx_index >= 0 && j.ctx_index < n_ctx && j.log2_max_tu >= 2 && j.log2_max_tu <= 5 && j.log2_min_tu_in_cu >= 2 && j.log2_min_tu_in_cu <= j.log2_max_tu &&
-              j.log2_cu - j.log2_min_tu_in_cu <= 3 && j.log2_cu - j.log2_max_tu <= 1 && j.lambda_rd > 0.0 && j.qp_scaled[0] >= 0 && j.qp_scaled[0] <= 87 && j.lambda_rdoq[0] > 0.0 &&
+    const int parts = 1 << (2 * (j.log2_cu - 2));
+    bool ok = rqt_class_ok(j) && cu_rect_ok(c, j) && j.ctx_index >= 0 && j.ctx_index < n_ctx && j.lambda_rd > 0.0 && j.qp_scaled[0] >= 0 && j.qp_scaled[0] <= 87 && j.lambda_rdoq[0] > 0.0 &&
               y.skip_ctx >= 0 && y.skip_ctx <= 2 && (y.tr_depth == 0 || y.tr_depth == 1) && !y.part_nxn == !y.tr_depth && y.part >= 0 && y.part < parts &&
               (y.part % (parts >> (2 * y.tr_depth))) == 0 && j.log2_cu - y.tr_depth >= j.log2_min_tu_in_cu;
     for (int p = 0; p < (y.part_nxn ? 4 : 1) && ok; p++) ok = y.luma_dir[p] >= 0 && y.luma_dir[p] < 35 && y.pred_num[p] >= 0 && y.pred_num[p] <= 3;
     if (!ok) return hop_set_err(c, HOP_ERR_ARG, "intra RQT job %d: illegal CU / PU node / transform-tree limits / syntax elements / snapshot / parameters", i);
-    coff[i + 1] = coff[i] + (((size_t)3 << (2 * j.log2_cu)) >> 1);
+    coff[i + 1] = coff[i] + cu_coeffs(j.log2_cu);
   }
-  for (int k = 0; k < n_ctx; k++) {
-    for (int i = 0; i < 150; i++) if (ctx_in[k].state[i] > 127) return hop_set_err(c, HOP_ERR_ARG, "context snapshot %d: state %d out of range", k, i);
-    for (int i = 0; i < 19; i++) if (cu_ctx_in[k].state[i] > 127) return hop_set_err(c, HOP_ERR_ARG, "CU context snapshot %d: state %d out of range", k, i);
-  }
-  std::vector<char> done(n, 0);
-  for (int first = 0; first < n; first++) {
-    if (done[first]) continue;
-    const hop_rqt_job& f = jobs[first]; const int d0 = syntax[first].tr_depth, cf = opts[first].check_first ? 1 : 0;
-    std::vector<int> idx; std::vector<hop_rqt_job> cls; std::vector<hop_intra_cu_syntax> sy; std::vector<hop_intra_rqt_opt> op;
-    for (int i = first; i < n; i++) {
-      const hop_rqt_job& j = jobs[i];
-      if (!done[i] && j.log2_cu == f.log2_cu && j.log2_max_tu == f.log2_max_tu && j.log2_min_tu_in_cu == f.log2_min_tu_in_cu && !j.sign_hide == !f.sign_hide && !j.use_ts == !f.use_ts &&
-          syntax[i].tr_depth == d0 && (opts[i].check_first ? 1 : 0) == cf) { done[i] = 1; idx.push_back(i); cls.push_back(j); sy.push_back(syntax[i]); op.push_back(opts[i]); }
-    }
-    const int m = (int)idx.size();
-    const size_t cu3 = ((size_t)3 << (2 * f.log2_cu)) / 2;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_j = 0, o_y = al((size_t)m * sizeof(hop_rqt_job)), o_p = al(o_y + (size_t)m * sizeof(hop_intra_cu_syntax)), o_c = al(o_p + (size_t)m * sizeof(hop_intra_rqt_opt));
-    const size_t o_u = al(o_c + (size_t)n_ctx * sizeof(hop_cabac_ctx)), o_r = al(o_u + (size_t)n_ctx * sizeof(hop_cabac_cu_ctx)), o_o = al(o_r + (size_t)m * sizeof(hop_rqt_result));
-    const size_t o_x = al(o_o + (size_t)m * cu3 * 4), o_v = al(o_x + (size_t)m * sizeof(hop_cabac_ctx)), o_e = al(o_v + (size_t)m * sizeof(hop_cabac_cu_ctx));
-    void* st; int r = hop_stage(c, o_e + 256, &st); if (r) return r;
-    char* b = (char*)st;
-    HIPCHK(c, hipMemcpyAsync(b + o_j, cls.data(), (size_t)m * sizeof(hop_rqt_job), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b + o_y, sy.data(), (size_t)m * sizeof(hop_intra_cu_syntax), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b + o_p, op.data(), (size_t)m * sizeof(hop_intra_rqt_opt), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b + o_c, ctx_in, (size_t)n_ctx * sizeof(hop_cabac_ctx), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b + o_u, cu_ctx_in, (size_t)n_ctx * sizeof(hop_cabac_cu_ctx), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(b + o_o, 0, (size_t)m * cu3 * 4, c->stream));
-    r = hop_intra_rqt_device(c, m, (const hop_rqt_job*)(b + o_j), &f, d0, cf, (const hop_intra_cu_syntax*)(b + o_y), (const hop_intra_rqt_opt*)(b + o_p), (const hop_cabac_ctx*)(b + o_c),
-                             (const hop_cabac_cu_ctx*)(b + o_u), (hop_rqt_result*)(b + o_r), (int32_t*)(b + o_o), (hop_cabac_ctx*)(b + o_x), (hop_cabac_cu_ctx*)(b + o_v));
-    if (r) return r;
-    std::vector<hop_rqt_result> rr(m); std::vector<int32_t> co((size_t)m * cu3); std::vector<hop_cabac_ctx> cx(m); std::vector<hop_cabac_cu_ctx> cv(m);
-    HIPCHK(c, hipMemcpyAsync(rr.data(), b + o_r, (size_t)m * sizeof(hop_rqt_result), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(co.data(), b + o_o, (size_t)m * cu3 * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(cx.data(), b + o_x, (size_t)m * sizeof(hop_cabac_ctx), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(cv.data(), b + o_v, (size_t)m * sizeof(hop_cabac_cu_ctx), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int t = 0; t < m; t++) {
-      results[idx[t]] = rr[t];
-      if (coef_out) memcpy(coef_out + coff[idx[t]], co.data() + (size_t)t * cu3, cu3 * 4);
-      if (ctx_out) ctx_out[idx[t]] = cx[t];
-      if (cu_ctx_out) cu_ctx_out[idx[t]] = cv[t];
-    }
-  }
-  return HOP_OK;
+  if (!ctx_states_ok(c, n_ctx, ctx_in, cu_ctx_in)) return HOP_ERR_ARG;
+  auto same = [&](int p, int q) {
+    return same_tree(jobs[p], jobs[q]) && !jobs[p].sign_hide == !jobs[q].sign_hide && syntax[p].tr_depth == syntax[q].tr_depth && !opts[p].check_first == !opts[q].check_first;
+  };
+  return for_each_class(n, same, [&](const std::vector<int>& idx) {
+    const hop_rqt_job& f = jobs[idx[0]]; const int d0 = syntax[idx[0]].tr_depth, cf = opts[idx[0]].check_first ? 1 : 0;
+    const size_t m = idx.size(), cu3 = cu_coeffs(f.log2_cu);
+    const std::vector<hop_rqt_job> cls = gather(jobs, idx); const std::vector<hop_intra_cu_syntax> sy = gather(syntax, idx); const std::vector<hop_intra_rqt_opt> op = gather(opts, idx);
+    stage_arena a(c);
+    auto dj = a.in(cls.data(), m); auto dy = a.in(sy.data(), m); auto dp = a.in(op.data(), m); auto dc = a.in(ctx_in, n_ctx); auto du = a.in(cu_ctx_in, n_ctx);
+    auto dr = a.out<hop_rqt_result>(m); auto d_co = a.zero<int32_t>(m * cu3); auto dx = a.out<hop_cabac_ctx>(m); auto dv = a.out<hop_cabac_cu_ctx>(m);
+    a.end_mark();
+    int r = a.commit(256); if (r) return r;
+    r = hop_intra_rqt_device(c, (int)m, a[dj], &f, d0, cf, a[dy], a[dp], a[dc], a[du], a[dr], a[d_co], a[dx], a[dv]); if (r) return r;
+    std::vector<hop_rqt_result> rr(m); std::vector<int32_t> co(m * cu3); std::vector<hop_cabac_ctx> cx(m); std::vector<hop_cabac_cu_ctx> cv(m);
+    if ((r = a.download(rr.data(), dr)) || (r = a.download(co.data(), d_co)) || (r = a.download(cx.data(), dx)) || (r = a.download(cv.data(), dv)) || (r = a.sync())) return r;
+    scatter(results, idx, rr.data());
+    if (coef_out) scatter(coef_out, idx, co.data(), cu3, coff.data());
+    if (ctx_out) scatter(ctx_out, idx, cx.data());
+    if (cu_ctx_out) scatter(cu_ctx_out, idx, cv.data());
+    return (int)HOP_OK;
+  });
 }
 
 int hop_intra_luma_search_device(hop_ctx* c, int n, const hop_rqt_job* d_jobs, const hop_rqt_job* cls, int part_nxn, int num_full_rd, const hop_intra_cu_syntax* d_syntax,
@@ -964,19 +904,10 @@ int hop_intra_luma_search_device(hop_ctx* c, int n, const hop_rqt_job* d_jobs, c
     return hop_set_err(c, HOP_ERR_ARG, "hop_intra_luma_search_device: bad argument");
   if (!c->have_orig) return hop_set_err(c, HOP_ERR_STATE, "hop_intra_luma_search: hop_upload_orig has not been called");
   const int nxn = part_nxn ? 1 : 0;
-  if (cls->log2_cu < 3 || cls->log2_cu > 6 || cls->log2_max_tu < 2 || cls->log2_max_tu > 5 || cls->log2_min_tu_in_cu < 2 || cls->log2_min_tu_in_cu > cls->log2_max_tu ||
-      cls->log2_cu - cls->log2_min_tu_in_cu > 3 || cls->log2_cu - cls->log2_max_tu > 1 || cls->log2_cu - nxn < cls->log2_min_tu_in_cu || num_full_rd < 1 || num_full_rd > 8)
+  if (!rqt_class_ok(*cls) || cls->log2_cu - nxn < cls->log2_min_tu_in_cu || num_full_rd < 1 || num_full_rd > 8)
     return hop_set_err(c, HOP_ERR_ARG, "hop_intra_luma_search_device: illegal CU class");
   if (n == 0) return HOP_OK;
-  const size_t wb = hop_intra_search_work_bytes(cls->log2_cu, n);
-  if (wb > c->rqt_bytes) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->rqt_buf) HIPCHK(c, hipFree(c->rqt_buf));
-    c->rqt_buf = nullptr; c->rqt_bytes = 0;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMalloc(&c->rqt_buf, wb + wb / 8));
-    c->rqt_bytes = wb + wb / 8;
-  }
+  int r = rqt_reserve(c, hop_intra_search_work_bytes(cls->log2_cu, n)); if (r) return r;
   return hop_launch_intra_search(c, cls->log2_cu, cls->log2_max_tu, cls->log2_min_tu_in_cu, cls->sign_hide ? 1 : 0, cls->use_ts ? 1 : 0, nxn, num_full_rd, n, d_jobs, d_syntax, d_opts,
                                  d_sjobs, d_ctx_in, d_cu_ctx_in, d_sresults, d_results, d_coef_out, d_reco_out, c->rqt_buf, c->rqt_bytes, nullptr);
 }
@@ -991,62 +922,34 @@ int hop_intra_luma_search(hop_ctx* c, int n, const hop_rqt_job* jobs, const hop_
   std::vector<size_t> coff(n + 1, 0), roff(n + 1, 0);
   for (int i = 0; i < n; i++) {
     const hop_rqt_job& j = jobs[i]; const hop_intra_cu_syntax& y = syntax[i]; const hop_intra_search_job& s = sjobs[i];
-    const int S = 1 << j.log2_cu, nxn = y.part_nxn ? 1 : 0;
-    bool ok = j.log2_cu >= 3 && j.log2_cu <= 6 && j.x >= 0 && j.y >= 0 && (j.x & (S - 1)) == 0 && (j.y & (S - 1)) == 0 && j.x + S <= c->pic_w && j.y + S <= c->pic_h &&
-              j.ctx_index >= 0 && j.ctx_index < n_ctx && j.log2_max_tu >= 2 && j.log2_max_tu <= 5 && j.log2_min_tu_in_cu >= 2 && j.log2_min_tu_in_cu <= j.log2_max_tu &&
-              j.log2_cu - j.log2_min_tu_in_cu <= 3 && j.log2_cu - j.log2_max_tu <= 1 && j.lambda_rd > 0.0 && j.qp_scaled[0] >= 0 && j.qp_scaled[0] <= 87 && j.lambda_rdoq[0] > 0.0 &&
+    const int nxn = y.part_nxn ? 1 : 0;
+    bool ok = rqt_class_ok(j) && cu_rect_ok(c, j) && j.ctx_index >= 0 && j.ctx_index < n_ctx && j.lambda_rd > 0.0 && j.qp_scaled[0] >= 0 && j.qp_scaled[0] <= 87 && j.lambda_rdoq[0] > 0.0 &&
               y.skip_ctx >= 0 && y.skip_ctx <= 2 && j.log2_cu - nxn >= j.log2_min_tu_in_cu && s.num_full_rd >= 1 && s.num_full_rd <= 8 && s.sqrt_lambda > 0.0;
     for (int p = 0; p < 4 && ok; p++) ok = s.left_dir[p] >= 0 && s.left_dir[p] < 35 && s.above_dir[p] >= 0 && s.above_dir[p] < 35;
     if (!ok) return hop_set_err(c, HOP_ERR_ARG, "intra search job %d: illegal CU / transform-tree limits / neighbour directions / snapshot / parameters", i);
-    coff[i + 1] = coff[i] + (((size_t)3 << (2 * j.log2_cu)) >> 1); roff[i + 1] = roff[i] + ((size_t)1 << (2 * j.log2_cu));
+    coff[i + 1] = coff[i] + cu_coeffs(j.log2_cu); roff[i + 1] = roff[i] + ((size_t)1 << (2 * j.log2_cu));
   }
-  for (int k = 0; k < n_ctx; k++) {
-    for (int i = 0; i < 150; i++) if (ctx_in[k].state[i] > 127) return hop_set_err(c, HOP_ERR_ARG, "context snapshot %d: state %d out of range", k, i);
-    for (int i = 0; i < 19; i++) if (cu_ctx_in[k].state[i] > 127) return hop_set_err(c, HOP_ERR_ARG, "CU context snapshot %d: state %d out of range", k, i);
-  }
-  std::vector<char> done(n, 0);
-  for (int first = 0; first < n; first++) {
-    if (done[first]) continue;
-    const hop_rqt_job& f = jobs[first]; const int nxn = syntax[first].part_nxn ? 1 : 0, nf = sjobs[first].num_full_rd;
-    std::vector<int> idx; std::vector<hop_rqt_job> cls; std::vector<hop_intra_cu_syntax> sy; std::vector<hop_intra_rqt_opt> op; std::vector<hop_intra_search_job> sj;
-    for (int i = first; i < n; i++) {
-      const hop_rqt_job& j = jobs[i];
-      if (!done[i] && j.log2_cu == f.log2_cu && j.log2_max_tu == f.log2_max_tu && j.log2_min_tu_in_cu == f.log2_min_tu_in_cu && !j.sign_hide == !f.sign_hide && !j.use_ts == !f.use_ts &&
-          (syntax[i].part_nxn ? 1 : 0) == nxn && sjobs[i].num_full_rd == nf) { done[i] = 1; idx.push_back(i); cls.push_back(j); sy.push_back(syntax[i]); op.push_back(opts[i]); sj.push_back(sjobs[i]); }
-    }
-    const int m = (int)idx.size();
-    const size_t cu2 = (size_t)1 << (2 * f.log2_cu), cu3 = cu2 + (cu2 >> 1);
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_j = 0, o_y = al((size_t)m * sizeof(hop_rqt_job)), o_p = al(o_y + (size_t)m * sizeof(hop_intra_cu_syntax)), o_s = al(o_p + (size_t)m * sizeof(hop_intra_rqt_opt));
-    const size_t o_c = al(o_s + (size_t)m * sizeof(hop_intra_search_job)), o_u = al(o_c + (size_t)n_ctx * sizeof(hop_cabac_ctx)), o_q = al(o_u + (size_t)n_ctx * sizeof(hop_cabac_cu_ctx));
-    const size_t o_r = al(o_q + (size_t)m * sizeof(hop_intra_search_result)), o_o = al(o_r + (size_t)m * sizeof(hop_rqt_result)), o_k = al(o_o + (size_t)m * cu3 * 4);
-    const size_t o_e = al(o_k + (size_t)m * cu2 * 2);
-    void* st; int r = hop_stage(c, o_e + 256, &st); if (r) return r;
-    char* b = (char*)st;
-    HIPCHK(c, hipMemcpyAsync(b + o_j, cls.data(), (size_t)m * sizeof(hop_rqt_job), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b + o_y, sy.data(), (size_t)m * sizeof(hop_intra_cu_syntax), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b + o_p, op.data(), (size_t)m * sizeof(hop_intra_rqt_opt), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b + o_s, sj.data(), (size_t)m * sizeof(hop_intra_search_job), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b + o_c, ctx_in, (size_t)n_ctx * sizeof(hop_cabac_ctx), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b + o_u, cu_ctx_in, (size_t)n_ctx * sizeof(hop_cabac_cu_ctx), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(b + o_q, 0, o_e - o_q, c->stream));
-    r = hop_intra_luma_search_device(c, m, (const hop_rqt_job*)(b + o_j), &f, nxn, nf, (const hop_intra_cu_syntax*)(b + o_y), (const hop_intra_rqt_opt*)(b + o_p),
-                                     (const hop_intra_search_job*)(b + o_s), (const hop_cabac_ctx*)(b + o_c), (const hop_cabac_cu_ctx*)(b + o_u), (hop_intra_search_result*)(b + o_q),
-                                     (hop_rqt_result*)(b + o_r), (int32_t*)(b + o_o), (int16_t*)(b + o_k));
-    if (r) return r;
-    std::vector<hop_intra_search_result> sr(m); std::vector<hop_rqt_result> rr(m); std::vector<int32_t> co((size_t)m * cu3); std::vector<int16_t> rk((size_t)m * cu2);
-    HIPCHK(c, hipMemcpyAsync(sr.data(), b + o_q, (size_t)m * sizeof(hop_intra_search_result), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(rr.data(), b + o_r, (size_t)m * sizeof(hop_rqt_result), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(co.data(), b + o_o, (size_t)m * cu3 * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(rk.data(), b + o_k, (size_t)m * cu2 * 2, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int t = 0; t < m; t++) {
-      sresults[idx[t]] = sr[t]; results[idx[t]] = rr[t];
-      memcpy(coef_out + coff[idx[t]], co.data() + (size_t)t * cu3, cu3 * 4);
-      memcpy(reco_out + roff[idx[t]], rk.data() + (size_t)t * cu2, cu2 * 2);
-    }
-  }
-  return HOP_OK;
+  if (!ctx_states_ok(c, n_ctx, ctx_in, cu_ctx_in)) return HOP_ERR_ARG;
+  auto same = [&](int p, int q) {
+    return same_tree(jobs[p], jobs[q]) && !jobs[p].sign_hide == !jobs[q].sign_hide && !syntax[p].part_nxn == !syntax[q].part_nxn && sjobs[p].num_full_rd == sjobs[q].num_full_rd;
+  };
+  return for_each_class(n, same, [&](const std::vector<int>& idx) {
+    const hop_rqt_job& f = jobs[idx[0]]; const int nxn = syntax[idx[0]].part_nxn ? 1 : 0, nf = sjobs[idx[0]].num_full_rd;
+    const size_t m = idx.size(), cu2 = (size_t)1 << (2 * f.log2_cu), cu3 = cu_coeffs(f.log2_cu);
+    const std::vector<hop_rqt_job> cls = gather(jobs, idx); const std::vector<hop_intra_cu_syntax> sy = gather(syntax, idx); const std::vector<hop_intra_rqt_opt> op = gather(opts, idx);
+    const std::vector<hop_intra_search_job> sj = gather(sjobs, idx);
+    stage_arena a(c);
+    auto dj = a.in(cls.data(), m); auto dy = a.in(sy.data(), m); auto dp = a.in(op.data(), m); auto ds = a.in(sj.data(), m); auto dc = a.in(ctx_in, n_ctx); auto du = a.in(cu_ctx_in, n_ctx);
+    auto dq = a.out<hop_intra_search_result>(m); auto dr = a.out<hop_rqt_result>(m); auto d_co = a.out<int32_t>(m * cu3); auto dk = a.out<int16_t>(m * cu2);
+    a.zero_span(dq, a.end_mark());                                     // every output starts cleared
+    int r = a.commit(256); if (r) return r;
+    r = hop_intra_luma_search_device(c, (int)m, a[dj], &f, nxn, nf, a[dy], a[dp], a[ds], a[dc], a[du], a[dq], a[dr], a[d_co], a[dk]); if (r) return r;
+    std::vector<hop_intra_search_result> sr(m); std::vector<hop_rqt_result> rr(m); std::vector<int32_t> co(m * cu3); std::vector<int16_t> rk(m * cu2);
+    if ((r = a.download(sr.data(), dq)) || (r = a.download(rr.data(), dr)) || (r = a.download(co.data(), d_co)) || (r = a.download(rk.data(), dk)) || (r = a.sync())) return r;
+    scatter(sresults, idx, sr.data()); scatter(results, idx, rr.data());
+    scatter(coef_out, idx, co.data(), cu3, coff.data()); scatter(reco_out, idx, rk.data(), cu2, roff.data());
+    return (int)HOP_OK;
+  });
 }
 
 int hop_intra_chroma_search_device(hop_ctx* c, int n, const hop_rqt_job* d_jobs, const hop_rqt_job* cls, const hop_intra_cu_syntax* d_syntax, const hop_intra_rqt_opt* d_opts,
@@ -1055,18 +958,9 @@ int hop_intra_chroma_search_device(hop_ctx* c, int n, const hop_rqt_job* d_jobs,
   if (!c || n < 0 || !cls || (n && (!d_jobs || !d_syntax || !d_opts || !d_ctx_in || !d_cu_ctx_in || !d_results || !d_cresults || !d_coef_out || !d_reco_out)))
     return hop_set_err(c, HOP_ERR_ARG, "hop_intra_chroma_search_device: bad argument");
   if (!c->have_orig) return hop_set_err(c, HOP_ERR_STATE, "hop_intra_chroma_search: hop_upload_orig has not been called");
-  if (cls->log2_cu < 3 || cls->log2_cu > 6 || cls->log2_max_tu < 2 || cls->log2_max_tu > 5 || cls->log2_min_tu_in_cu < 2 || cls->log2_min_tu_in_cu > cls->log2_max_tu ||
-      cls->log2_cu - cls->log2_min_tu_in_cu > 3 || cls->log2_cu - cls->log2_max_tu > 1) return hop_set_err(c, HOP_ERR_ARG, "hop_intra_chroma_search_device: illegal CU class");
+  if (!rqt_class_ok(*cls)) return hop_set_err(c, HOP_ERR_ARG, "hop_intra_chroma_search_device: illegal CU class");
   if (n == 0) return HOP_OK;
-  const size_t wb = hop_intra_chroma_work_bytes(cls->log2_cu, n);
-  if (wb > c->rqt_bytes) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->rqt_buf) HIPCHK(c, hipFree(c->rqt_buf));
-    c->rqt_buf = nullptr; c->rqt_bytes = 0;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMalloc(&c->rqt_buf, wb + wb / 8));
-    c->rqt_bytes = wb + wb / 8;
-  }
+  int r = rqt_reserve(c, hop_intra_chroma_work_bytes(cls->log2_cu, n)); if (r) return r;
   return hop_launch_intra_chroma_search(c, cls->log2_cu, cls->log2_max_tu, cls->log2_min_tu_in_cu, cls->sign_hide ? 1 : 0, cls->use_ts ? 1 : 0, n, d_jobs, d_syntax, d_opts, d_ctx_in,
                                         d_cu_ctx_in, d_results, d_cresults, d_coef_out, d_reco_out, c->rqt_buf, c->rqt_bytes, nullptr);
 }
@@ -1080,10 +974,8 @@ int hop_intra_chroma_search(hop_ctx* c, int n, const hop_rqt_job* jobs, const ho
   std::vector<size_t> coff(n + 1, 0), roff(n + 1, 0);
   for (int i = 0; i < n; i++) {
     const hop_rqt_job& j = jobs[i]; const hop_intra_cu_syntax& y = syntax[i];
-    const int S = 1 << j.log2_cu, parts = 1 << (2 * (j.log2_cu - 2));
-    bool ok = j.log2_cu >= 3 && j.log2_cu <= 6 && j.x >= 0 && j.y >= 0 && (j.x & (S - 1)) == 0 && (j.y & (S - 1)) == 0 && j.x + S <= c->pic_w && j.y + S <= c->pic_h &&
-              j.ctx_index >= 0 && j.ctx_index < n_ctx && j.log2_max_tu >= 2 && j.log2_max_tu <= 5 && j.log2_min_tu_in_cu >= 2 && j.log2_min_tu_in_cu <= j.log2_max_tu &&
-              j.log2_cu - j.log2_min_tu_in_cu <= 3 && j.log2_cu - j.log2_max_tu <= 1 && j.lambda_rd > 0.0 && y.luma_dir[0] >= 0 && y.luma_dir[0] < 35;
+    const int parts = 1 << (2 * (j.log2_cu - 2));
+    bool ok = rqt_class_ok(j) && cu_rect_ok(c, j) && j.ctx_index >= 0 && j.ctx_index < n_ctx && j.lambda_rd > 0.0 && y.luma_dir[0] >= 0 && y.luma_dir[0] < 35;
     for (int k = 1; k < 3 && ok; k++) ok = j.qp_scaled[k] >= 0 && j.qp_scaled[k] <= 87 && j.lambda_rdoq[k] > 0.0;
     // the luma tree must be a legal tree of the class: every depth within the limits, quadrants consistent
     for (int p = 0; p < parts && ok; p++) {
@@ -1091,62 +983,34 @@ int hop_intra_chroma_search(hop_ctx* c, int n, const hop_rqt_job* jobs, const ho
       ok = d >= 0 && d <= 3 && lg >= j.log2_min_tu_in_cu && lg <= j.log2_max_tu && results[i].tr_idx[p - p % (parts >> (2 * d))] == d && results[i].tskip[0][p] <= 1;
     }
     if (!ok) return hop_set_err(c, HOP_ERR_ARG, "intra chroma search job %d: illegal CU / transform-tree limits / luma tree / snapshot / parameters", i);
-    coff[i + 1] = coff[i] + (((size_t)3 << (2 * j.log2_cu)) >> 1); roff[i + 1] = roff[i] + ((size_t)1 << (2 * j.log2_cu - 1));
+    coff[i + 1] = coff[i] + cu_coeffs(j.log2_cu); roff[i + 1] = roff[i] + ((size_t)1 << (2 * j.log2_cu - 1));
   }
-  for (int k = 0; k < n_ctx; k++) {
-    for (int i = 0; i < 150; i++) if (ctx_in[k].state[i] > 127) return hop_set_err(c, HOP_ERR_ARG, "context snapshot %d: state %d out of range", k, i);
-    for (int i = 0; i < 19; i++) if (cu_ctx_in[k].state[i] > 127) return hop_set_err(c, HOP_ERR_ARG, "CU context snapshot %d: state %d out of range", k, i);
-  }
-  std::vector<char> done(n, 0);
-  for (int first = 0; first < n; first++) {
-    if (done[first]) continue;
-    const hop_rqt_job& f = jobs[first];
-    std::vector<int> idx; std::vector<hop_rqt_job> cls; std::vector<hop_intra_cu_syntax> sy; std::vector<hop_intra_rqt_opt> op; std::vector<hop_rqt_result> rr;
-    for (int i = first; i < n; i++) {
-      const hop_rqt_job& j = jobs[i];
-      if (!done[i] && j.log2_cu == f.log2_cu && j.log2_max_tu == f.log2_max_tu && j.log2_min_tu_in_cu == f.log2_min_tu_in_cu && !j.sign_hide == !f.sign_hide && !j.use_ts == !f.use_ts) {
-        done[i] = 1; idx.push_back(i); cls.push_back(j); sy.push_back(syntax[i]); op.push_back(opts[i]); rr.push_back(results[i]);
-      }
-    }
-    const int m = (int)idx.size();
-    const size_t cu2 = (size_t)1 << (2 * f.log2_cu), cu3 = cu2 + (cu2 >> 1), h2x2 = cu2 >> 1;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_j = 0, o_y = al((size_t)m * sizeof(hop_rqt_job)), o_p = al(o_y + (size_t)m * sizeof(hop_intra_cu_syntax)), o_c = al(o_p + (size_t)m * sizeof(hop_intra_rqt_opt));
-    const size_t o_u = al(o_c + (size_t)n_ctx * sizeof(hop_cabac_ctx)), o_r = al(o_u + (size_t)n_ctx * sizeof(hop_cabac_cu_ctx)), o_q = al(o_r + (size_t)m * sizeof(hop_rqt_result));
-    const size_t o_o = al(o_q + (size_t)m * sizeof(hop_intra_chroma_result)), o_k = al(o_o + (size_t)m * cu3 * 4), o_e = al(o_k + (size_t)m * h2x2 * 2);
-    void* st; int r = hop_stage(c, o_e + 256, &st); if (r) return r;
-    char* b = (char*)st;
-    HIPCHK(c, hipMemcpyAsync(b + o_j, cls.data(), (size_t)m * sizeof(hop_rqt_job), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b + o_y, sy.data(), (size_t)m * sizeof(hop_intra_cu_syntax), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b + o_p, op.data(), (size_t)m * sizeof(hop_intra_rqt_opt), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b + o_c, ctx_in, (size_t)n_ctx * sizeof(hop_cabac_ctx), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b + o_u, cu_ctx_in, (size_t)n_ctx * sizeof(hop_cabac_cu_ctx), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b + o_r, rr.data(), (size_t)m * sizeof(hop_rqt_result), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(b + o_q, 0, o_e - o_q, c->stream));
-    r = hop_intra_chroma_search_device(c, m, (const hop_rqt_job*)(b + o_j), &f, (const hop_intra_cu_syntax*)(b + o_y), (const hop_intra_rqt_opt*)(b + o_p), (const hop_cabac_ctx*)(b + o_c),
-                                       (const hop_cabac_cu_ctx*)(b + o_u), (hop_rqt_result*)(b + o_r), (hop_intra_chroma_result*)(b + o_q), (int32_t*)(b + o_o), (int16_t*)(b + o_k));
-    if (r) return r;
-    std::vector<hop_intra_chroma_result> cr(m); std::vector<int32_t> co((size_t)m * cu3); std::vector<int16_t> rk((size_t)m * h2x2);
-    HIPCHK(c, hipMemcpyAsync(rr.data(), b + o_r, (size_t)m * sizeof(hop_rqt_result), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(cr.data(), b + o_q, (size_t)m * sizeof(hop_intra_chroma_result), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(co.data(), b + o_o, (size_t)m * cu3 * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(rk.data(), b + o_k, (size_t)m * h2x2 * 2, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int t = 0; t < m; t++) {
-      results[idx[t]] = rr[t]; cresults[idx[t]] = cr[t];
-      memcpy(coef_out + coff[idx[t]] + cu2, co.data() + (size_t)t * cu3 + cu2, (cu2 >> 1) * 4);
-      memcpy(reco_out + roff[idx[t]], rk.data() + (size_t)t * h2x2, h2x2 * 2);
-    }
-  }
-  return HOP_OK;
+  if (!ctx_states_ok(c, n_ctx, ctx_in, cu_ctx_in)) return HOP_ERR_ARG;
+  return for_each_class(n, [&](int p, int q) { return same_tree(jobs[p], jobs[q]) && !jobs[p].sign_hide == !jobs[q].sign_hide; }, [&](const std::vector<int>& idx) {
+    const hop_rqt_job& f = jobs[idx[0]];
+    const size_t m = idx.size(), cu2 = (size_t)1 << (2 * f.log2_cu), cu3 = cu_coeffs(f.log2_cu), h2x2 = cu2 >> 1;
+    const std::vector<hop_rqt_job> cls = gather(jobs, idx); const std::vector<hop_intra_cu_syntax> sy = gather(syntax, idx); const std::vector<hop_intra_rqt_opt> op = gather(opts, idx);
+    std::vector<hop_rqt_result> rr = gather(results, idx);
+    stage_arena a(c);
+    auto dj = a.in(cls.data(), m); auto dy = a.in(sy.data(), m); auto dp = a.in(op.data(), m); auto dc = a.in(ctx_in, n_ctx); auto du = a.in(cu_ctx_in, n_ctx); auto dr = a.in(rr.data(), m);
+    auto dq = a.out<hop_intra_chroma_result>(m); auto d_co = a.out<int32_t>(m * cu3); auto dk = a.out<int16_t>(m * h2x2);
+    a.zero_span(dq, a.end_mark());                                     // every output starts cleared
+    int r = a.commit(256); if (r) return r;
+    r = hop_intra_chroma_search_device(c, (int)m, a[dj], &f, a[dy], a[dp], a[dc], a[du], a[dr], a[dq], a[d_co], a[dk]); if (r) return r;
+    std::vector<hop_intra_chroma_result> cr(m); std::vector<int32_t> co(m * cu3); std::vector<int16_t> rk(m * h2x2);
+    if ((r = a.download(rr.data(), dr)) || (r = a.download(cr.data(), dq)) || (r = a.download(co.data(), d_co)) || (r = a.download(rk.data(), dk)) || (r = a.sync())) return r;
+    scatter(results, idx, rr.data()); scatter(cresults, idx, cr.data());
+    scatter(coef_out + cu2, idx, co.data() + cu2, cu2 >> 1, coff.data(), cu3);       // the chroma levels of the CU only
+    scatter(reco_out, idx, rk.data(), h2x2, roff.data());
+    return (int)HOP_OK;
+  });
 }
 
 int hop_intra_cu_total_bits_device(hop_ctx* c, int n, const hop_rqt_job* d_jobs, const hop_rqt_job* cls, const hop_intra_cu_syntax* d_syntax, const hop_rqt_result* d_results,
                                    const int32_t* d_coef, const uint32_t* d_dist, const hop_cabac_ctx* d_ctx_in, const hop_cabac_cu_ctx* d_cu_ctx_in, uint32_t* d_bits, double* d_cost,
                                    hop_cabac_ctx* d_ctx_out, hop_cabac_cu_ctx* d_cu_ctx_out) {
   if (!c || n < 0 || !cls || (n && (!d_jobs || !d_syntax || !d_results || !d_coef || !d_ctx_in || !d_cu_ctx_in || !d_bits))) return hop_set_err(c, HOP_ERR_ARG, "hop_intra_cu_total_bits_device: bad argument");
-  if (cls->log2_cu < 3 || cls->log2_cu > 6 || cls->log2_max_tu < 2 || cls->log2_max_tu > 5 || cls->log2_min_tu_in_cu < 2 || cls->log2_min_tu_in_cu > cls->log2_max_tu ||
-      cls->log2_cu - cls->log2_min_tu_in_cu > 3 || cls->log2_cu - cls->log2_max_tu > 1) return hop_set_err(c, HOP_ERR_ARG, "hop_intra_cu_total_bits_device: illegal CU class");
+  if (!rqt_class_ok(*cls)) return hop_set_err(c, HOP_ERR_ARG, "hop_intra_cu_total_bits_device: illegal CU class");
   if (n == 0) return HOP_OK;
   return hop_launch_intra_cu_total(c, cls->log2_cu, cls->log2_max_tu, cls->log2_min_tu_in_cu, cls->sign_hide ? 1 : 0, cls->use_ts ? 1 : 0, n, d_jobs, d_syntax, d_results, d_coef, d_ctx_in,
                                    d_cu_ctx_in, d_dist, d_bits, d_cost, d_ctx_out, d_cu_ctx_out);
@@ -1161,61 +1025,35 @@ int hop_intra_cu_total_bits(hop_ctx* c, int n, const hop_rqt_job* jobs, const ho
   for (int i = 0; i < n; i++) {
     const hop_rqt_job& j = jobs[i]; const hop_intra_cu_syntax& y = syntax[i];
     const int parts = 1 << (2 * (j.log2_cu - 2));
-    bool ok = j.log2_cu >= 3 && j.log2_cu <= 6 && j.ctx_index >= 0 && j.ctx_index < n_ctx && j.log2_max_tu >= 2 && j.log2_max_tu <= 5 && j.log2_min_tu_in_cu >= 2 &&
-              j.log2_min_tu_in_cu <= j.log2_max_tu && j.log2_cu - j.log2_min_tu_in_cu <= 3 && j.log2_cu - j.log2_max_tu <= 1 && j.lambda_rd > 0.0 && y.skip_ctx >= 0 && y.skip_ctx <= 2;
+    bool ok = rqt_class_ok(j) && j.ctx_index >= 0 && j.ctx_index < n_ctx && j.lambda_rd > 0.0 && y.skip_ctx >= 0 && y.skip_ctx <= 2;
     for (int p = 0; p < (y.part_nxn ? 4 : 1) && ok; p++) ok = y.luma_dir[p] >= 0 && y.luma_dir[p] < 35 && y.pred_num[p] >= 0 && y.pred_num[p] <= 3;
     for (int p = 0; p < parts && ok; p++) {
       const int d = results[i].tr_idx[p], lg = j.log2_cu - d;
       ok = d >= (y.part_nxn ? 1 : 0) && d <= 3 && lg >= j.log2_min_tu_in_cu && lg <= j.log2_max_tu && results[i].tr_idx[p - p % (parts >> (2 * d))] == d;
     }
     if (!ok) return hop_set_err(c, HOP_ERR_ARG, "intra CU bits job %d: illegal CU class / syntax elements / transform tree / snapshot", i);
-    coff[i + 1] = coff[i] + (((size_t)3 << (2 * j.log2_cu)) >> 1);
+    coff[i + 1] = coff[i] + cu_coeffs(j.log2_cu);
   }
-  for (int k = 0; k < n_ctx; k++) {
-    for (int i = 0; i < 150; i++) if (ctx_in[k].state[i] > 127) return hop_set_err(c, HOP_ERR_ARG, "context snapshot %d: state %d out of range", k, i);
-    for (int i = 0; i < 19; i++) if (cu_ctx_in[k].state[i] > 127) return hop_set_err(c, HOP_ERR_ARG, "CU context snapshot %d: state %d out of range", k, i);
-  }
-  std::vector<char> done(n, 0);
-  for (int first = 0; first < n; first++) {
-    if (done[first]) continue;
-    const hop_rqt_job& f = jobs[first];
-    std::vector<int> idx; std::vector<hop_rqt_job> cls; std::vector<hop_intra_cu_syntax> sy; std::vector<hop_rqt_result> rr; std::vector<uint32_t> dd;
-    for (int i = first; i < n; i++) {
-      const hop_rqt_job& j = jobs[i];
-      if (!done[i] && j.log2_cu == f.log2_cu && j.log2_max_tu == f.log2_max_tu && j.log2_min_tu_in_cu == f.log2_min_tu_in_cu && !j.sign_hide == !f.sign_hide && !j.use_ts == !f.use_ts) {
-        done[i] = 1; idx.push_back(i); cls.push_back(j); sy.push_back(syntax[i]); rr.push_back(results[i]); dd.push_back(dist[i]);
-      }
-    }
-    const int m = (int)idx.size();
-    const size_t cu3 = ((size_t)3 << (2 * f.log2_cu)) / 2;
-    std::vector<int32_t> co((size_t)m * cu3);
-    for (int t = 0; t < m; t++) memcpy(co.data() + (size_t)t * cu3, coef + coff[idx[t]], cu3 * 4);
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_j = 0, o_y = al((size_t)m * sizeof(hop_rqt_job)), o_r = al(o_y + (size_t)m * sizeof(hop_intra_cu_syntax)), o_o = al(o_r + (size_t)m * sizeof(hop_rqt_result));
-    const size_t o_d = al(o_o + (size_t)m * cu3 * 4), o_c = al(o_d + (size_t)m * 4), o_u = al(o_c + (size_t)n_ctx * sizeof(hop_cabac_ctx)), o_b = al(o_u + (size_t)n_ctx * sizeof(hop_cabac_cu_ctx));
-    const size_t o_k = al(o_b + (size_t)m * 4), o_x = al(o_k + (size_t)m * 8), o_v = al(o_x + (size_t)m * sizeof(hop_cabac_ctx)), o_e = al(o_v + (size_t)m * sizeof(hop_cabac_cu_ctx));
-    void* st; int r = hop_stage(c, o_e + 256, &st); if (r) return r;
-    char* b = (char*)st;
-    HIPCHK(c, hipMemcpyAsync(b + o_j, cls.data(), (size_t)m * sizeof(hop_rqt_job), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b + o_y, sy.data(), (size_t)m * sizeof(hop_intra_cu_syntax), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b + o_r, rr.data(), (size_t)m * sizeof(hop_rqt_result), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b + o_o, co.data(), (size_t)m * cu3 * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b + o_d, dd.data(), (size_t)m * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b + o_c, ctx_in, (size_t)n_ctx * sizeof(hop_cabac_ctx), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b + o_u, cu_ctx_in, (size_t)n_ctx * sizeof(hop_cabac_cu_ctx), hipMemcpyHostToDevice, c->stream));
-    r = hop_intra_cu_total_bits_device(c, m, (const hop_rqt_job*)(b + o_j), &f, (const hop_intra_cu_syntax*)(b + o_y), (const hop_rqt_result*)(b + o_r), (const int32_t*)(b + o_o),
-                                       (const uint32_t*)(b + o_d), (const hop_cabac_ctx*)(b + o_c), (const hop_cabac_cu_ctx*)(b + o_u), (uint32_t*)(b + o_b), (double*)(b + o_k),
-                                       (hop_cabac_ctx*)(b + o_x), (hop_cabac_cu_ctx*)(b + o_v));
-    if (r) return r;
+  if (!ctx_states_ok(c, n_ctx, ctx_in, cu_ctx_in)) return HOP_ERR_ARG;
+  return for_each_class(n, [&](int p, int q) { return same_tree(jobs[p], jobs[q]) && !jobs[p].sign_hide == !jobs[q].sign_hide; }, [&](const std::vector<int>& idx) {
+    const hop_rqt_job& f = jobs[idx[0]];
+    const size_t m = idx.size(), cu3 = cu_coeffs(f.log2_cu);
+    const std::vector<hop_rqt_job> cls = gather(jobs, idx); const std::vector<hop_intra_cu_syntax> sy = gather(syntax, idx); const std::vector<hop_rqt_result> rr = gather(results, idx);
+    const std::vector<int32_t> co = gather(coef, idx, cu3, coff.data()); const std::vector<uint32_t> dd = gather(dist, idx);
+    stage_arena a(c);
+    auto dj = a.in(cls.data(), m); auto dy = a.in(sy.data(), m); auto dr = a.in(rr.data(), m); auto d_co = a.in(co.data(), m * cu3); auto d_di = a.in(dd.data(), m);
+    auto dc = a.in(ctx_in, n_ctx); auto du = a.in(cu_ctx_in, n_ctx);
+    auto db = a.out<uint32_t>(m); auto dk = a.out<double>(m); auto dx = a.out<hop_cabac_ctx>(m); auto dv = a.out<hop_cabac_cu_ctx>(m);
+    a.end_mark();
+    int r = a.commit(256); if (r) return r;
+    r = hop_intra_cu_total_bits_device(c, (int)m, a[dj], &f, a[dy], a[dr], a[d_co], a[d_di], a[dc], a[du], a[db], a[dk], a[dx], a[dv]); if (r) return r;
     std::vector<uint32_t> bb(m); std::vector<double> kk(m); std::vector<hop_cabac_ctx> cx(m); std::vector<hop_cabac_cu_ctx> cv(m);
-    HIPCHK(c, hipMemcpyAsync(bb.data(), b + o_b, (size_t)m * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(kk.data(), b + o_k, (size_t)m * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(cx.data(), b + o_x, (size_t)m * sizeof(hop_cabac_ctx), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(cv.data(), b + o_v, (size_t)m * sizeof(hop_cabac_cu_ctx), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int t = 0; t < m; t++) { bits[idx[t]] = bb[t]; cost[idx[t]] = kk[t]; if (ctx_out) ctx_out[idx[t]] = cx[t]; if (cu_ctx_out) cu_ctx_out[idx[t]] = cv[t]; }
-  }
-  return HOP_OK;
+    if ((r = a.download(bb.data(), db)) || (r = a.download(kk.data(), dk)) || (r = a.download(cx.data(), dx)) || (r = a.download(cv.data(), dv)) || (r = a.sync())) return r;
+    scatter(bits, idx, bb.data()); scatter(cost, idx, kk.data());
+    if (ctx_out) scatter(ctx_out, idx, cx.data());
+    if (cu_ctx_out) scatter(cu_ctx_out, idx, cv.data());
+    return (int)HOP_OK;
+  });
 }
 
 int hop_inter_cu_skip_device(hop_ctx* c, int n, const hop_rqt_job* d_jobs, const hop_cu_syntax* d_syntax, const hop_cabac_ctx* d_ctx_in, const hop_cabac_cu_ctx* d_cu_ctx_in,
@@ -1233,48 +1071,21 @@ int hop_inter_cu_skip(hop_ctx* c, int n, const hop_rqt_job* jobs, const hop_cu_s
   if (n == 0) return HOP_OK;
   for (int i = 0; i < n; i++) {
     const hop_rqt_job& j = jobs[i]; const hop_cu_syntax& y = syntax[i];
-    const int S = 1 << j.log2_cu;
-    const bool ok = j.log2_cu >= 3 && j.log2_cu <= 6 && j.x >= 0 && j.y >= 0 && (j.x & (S - 1)) == 0 && (j.y & (S - 1)) == 0 && j.x + S <= c->pic_w && j.y + S <= c->pic_h &&
-                    j.ctx_index >= 0 && j.ctx_index < n_ctx && j.lambda_rd > 0.0 && y.skip_ctx >= 0 && y.skip_ctx <= 2 && y.max_merge_cand >= 1 && y.max_merge_cand <= 5 &&
+    const bool ok = cu_rect_ok(c, j) && j.ctx_index >= 0 && j.ctx_index < n_ctx && j.lambda_rd > 0.0 && y.skip_ctx >= 0 && y.skip_ctx <= 2 && y.max_merge_cand >= 1 && y.max_merge_cand <= 5 &&
                     y.pu[0].merge_idx >= 0 && y.pu[0].merge_idx < y.max_merge_cand;
     if (!ok) return hop_set_err(c, HOP_ERR_ARG, "skip candidate %d: illegal CU / snapshot / merge index / parameters", i);
   }
-  for (int k = 0; k < n_ctx; k++) {
-    for (int i = 0; i < 150; i++) if (ctx_in[k].state[i] > 127) return hop_set_err(c, HOP_ERR_ARG, "context snapshot %d: state %d out of range", k, i);
-    for (int i = 0; i < 19; i++) if (cu_ctx_in[k].state[i] > 127) return hop_set_err(c, HOP_ERR_ARG, "CU context snapshot %d: state %d out of range", k, i);
-  }
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t o_j = 0, o_y = al((size_t)n * sizeof(hop_rqt_job)), o_c = al(o_y + (size_t)n * sizeof(hop_cu_syntax)), o_u = al(o_c + (size_t)n_ctx * sizeof(hop_cabac_ctx));
-  const size_t o_f = al(o_u + (size_t)n_ctx * sizeof(hop_cabac_cu_ctx)), o_b = al(o_f + (size_t)n * sizeof(hop_cu_final)), o_k = al(o_b + (size_t)n * 4), o_x = al(o_k + (size_t)n * 8);
-  const size_t o_v = al(o_x + (size_t)n * sizeof(hop_cabac_ctx)), o_e = al(o_v + (size_t)n * sizeof(hop_cabac_cu_ctx));
-  void* st; int r = hop_stage(c, o_e + 256, &st); if (r) return r;
-  char* b = (char*)st;
-  HIPCHK(c, hipMemcpyAsync(b + o_j, jobs, (size_t)n * sizeof(hop_rqt_job), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(b + o_y, syntax, (size_t)n * sizeof(hop_cu_syntax), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(b + o_c, ctx_in, (size_t)n_ctx * sizeof(hop_cabac_ctx), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(b + o_u, cu_ctx_in, (size_t)n_ctx * sizeof(hop_cabac_cu_ctx), hipMemcpyHostToDevice, c->stream));
-  r = hop_inter_cu_skip_device(c, n, (const hop_rqt_job*)(b + o_j), (const hop_cu_syntax*)(b + o_y), (const hop_cabac_ctx*)(b + o_c), (const hop_cabac_cu_ctx*)(b + o_u),
-                               (hop_cu_final*)(b + o_f), (uint32_t*)(b + o_b), (double*)(b + o_k), (hop_cabac_ctx*)(b + o_x), (hop_cabac_cu_ctx*)(b + o_v));
-  if (r) return r;
-  HIPCHK(c, hipMemcpyAsync(finals, b + o_f, (size_t)n * sizeof(hop_cu_final), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(bits, b + o_b, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(cost, b + o_k, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-  if (ctx_out) HIPCHK(c, hipMemcpyAsync(ctx_out, b + o_x, (size_t)n * sizeof(hop_cabac_ctx), hipMemcpyDeviceToHost, c->stream));
-  if (cu_ctx_out) HIPCHK(c, hipMemcpyAsync(cu_ctx_out, b + o_v, (size_t)n * sizeof(hop_cabac_cu_ctx), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return HOP_OK;
-}
-
-// grows c->walk_buf (synchronises the stream first when it has to reallocate)
-static int hop_walk_reserve(hop_ctx* c, size_t bytes) {
-  if (bytes <= c->walk_bytes) return HOP_OK;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (c->walk_buf) HIPCHK(c, hipFree(c->walk_buf));
-  c->walk_buf = nullptr; c->walk_bytes = 0;
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipMalloc(&c->walk_buf, bytes + bytes / 4));
-  c->walk_bytes = bytes + bytes / 4;
-  return HOP_OK;
+  if (!ctx_states_ok(c, n_ctx, ctx_in, cu_ctx_in)) return HOP_ERR_ARG;
+  stage_arena a(c);
+  auto dj = a.in(jobs, n); auto dy = a.in(syntax, n); auto dc = a.in(ctx_in, n_ctx); auto du = a.in(cu_ctx_in, n_ctx);
+  auto df = a.out<hop_cu_final>(n); auto db = a.out<uint32_t>(n); auto dk = a.out<double>(n); auto dx = a.out<hop_cabac_ctx>(n); auto dv = a.out<hop_cabac_cu_ctx>(n);
+  a.end_mark();
+  int r = a.commit(256); if (r) return r;
+  r = hop_inter_cu_skip_device(c, n, a[dj], a[dy], a[dc], a[du], a[df], a[db], a[dk], a[dx], a[dv]); if (r) return r;
+  if ((r = a.download(finals, df)) || (r = a.download(bits, db)) || (r = a.download(cost, dk))) return r;
+  if (ctx_out && (r = a.download(ctx_out, dx))) return r;
+  if (cu_ctx_out && (r = a.download(cu_ctx_out, dv))) return r;
+  return a.sync();
 }
 
 // one class of intra candidates, device-resident from the rough search to the cost: luma search -> chroma search -> bits and cost, no host step in between
@@ -1284,27 +1095,17 @@ static int intra_candidate_chain(hop_ctx* c, const hop_intra_class& k, const hop
   if (k.n < 0 || (k.n && (!k.d_jobs || !k.d_syntax || !k.d_opts || !k.d_sjobs || !k.d_sresults || !k.d_results || !k.d_cresults || !k.d_coef || !k.d_reco_y || !k.d_reco_c ||
                           !k.d_syntax_out || !k.d_dist || !k.d_bits || !k.d_cost)))
     return hop_set_err(c, HOP_ERR_ARG, "hop_intra_cu_device_classes: bad class descriptor");
-  if (cls->log2_cu < 3 || cls->log2_cu > 6 || cls->log2_max_tu < 2 || cls->log2_max_tu > 5 || cls->log2_min_tu_in_cu < 2 || cls->log2_min_tu_in_cu > cls->log2_max_tu ||
-      cls->log2_cu - cls->log2_min_tu_in_cu > 3 || cls->log2_cu - cls->log2_max_tu > 1 || cls->log2_cu - nxn < cls->log2_min_tu_in_cu || k.num_full_rd < 1 || k.num_full_rd > 8)
+  if (!rqt_class_ok(*cls) || cls->log2_cu - nxn < cls->log2_min_tu_in_cu || k.num_full_rd < 1 || k.num_full_rd > 8)
     return hop_set_err(c, HOP_ERR_ARG, "hop_intra_cu_device_classes: illegal CU class");
   if (k.n == 0) return HOP_OK;
   if (k.n <= c->walk_max && !getenv("HOP_WALK_NO_INTRA")) {              // the RD spine's batches: one kernel per candidate (k_walk.inl)
-    int r = hop_walk_reserve(c, hop_intra_walk_bytes(c, cls->log2_cu, k.n, k.num_full_rd)); if (r) return r;
+    int r = walk_reserve(c, hop_intra_walk_bytes(c, cls->log2_cu, k.n, k.num_full_rd)); if (r) return r;
     return hop_launch_intra_walk(c, k, d_ctx_in, d_cu_ctx_in, c->walk_buf, c->walk_bytes);
   }
-  size_t wb = hop_intra_search_work_bytes(cls->log2_cu, k.n); const size_t wc = hop_intra_chroma_work_bytes(cls->log2_cu, k.n);
-  if (wc > wb) wb = wc;
-  if (wb > c->rqt_bytes) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->rqt_buf) HIPCHK(c, hipFree(c->rqt_buf));
-    c->rqt_buf = nullptr; c->rqt_bytes = 0;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMalloc(&c->rqt_buf, wb + wb / 8));
-    c->rqt_bytes = wb + wb / 8;
-  }
+  int r = rqt_reserve(c, std::max(hop_intra_search_work_bytes(cls->log2_cu, k.n), hop_intra_chroma_work_bytes(cls->log2_cu, k.n))); if (r) return r;
   const int sh = cls->sign_hide ? 1 : 0, ts = cls->use_ts ? 1 : 0;
-  int r = hop_launch_intra_search(c, cls->log2_cu, cls->log2_max_tu, cls->log2_min_tu_in_cu, sh, ts, nxn, k.num_full_rd, k.n, k.d_jobs, k.d_syntax, k.d_opts, k.d_sjobs, d_ctx_in, d_cu_ctx_in,
-                                  k.d_sresults, k.d_results, k.d_coef, k.d_reco_y, c->rqt_buf, c->rqt_bytes, k.d_syntax_out);
+  r = hop_launch_intra_search(c, cls->log2_cu, cls->log2_max_tu, cls->log2_min_tu_in_cu, sh, ts, nxn, k.num_full_rd, k.n, k.d_jobs, k.d_syntax, k.d_opts, k.d_sjobs, d_ctx_in, d_cu_ctx_in,
+                              k.d_sresults, k.d_results, k.d_coef, k.d_reco_y, c->rqt_buf, c->rqt_bytes, k.d_syntax_out);
   if (r) return r;
   r = hop_launch_intra_chroma_search(c, cls->log2_cu, cls->log2_max_tu, cls->log2_min_tu_in_cu, sh, ts, k.n, k.d_jobs, k.d_syntax_out, k.d_opts, d_ctx_in, d_cu_ctx_in, k.d_results,
                                      k.d_cresults, k.d_coef, k.d_reco_c, c->rqt_buf, c->rqt_bytes, k.d_syntax_out);
@@ -1316,13 +1117,11 @@ static int intra_candidate_chain(hop_ctx* c, const hop_intra_class& k, const hop
                                    k.d_bits, k.d_cost, k.d_ctx_out, k.d_cu_ctx_out);
 }
 
-static int intra_classes_issue(hop_ctx* c, int n_classes, const hop_intra_class* classes, const hop_cabac_ctx* d_ctx_in, const hop_cabac_cu_ctx* d_cu_ctx_in);
-
 int hop_intra_cu_device_classes(hop_ctx* c, int n_classes, const hop_intra_class* classes, const hop_cabac_ctx* d_ctx_in, const hop_cabac_cu_ctx* d_cu_ctx_in) {
   if (!c || n_classes < 0 || (n_classes && (!classes || !d_ctx_in || !d_cu_ctx_in))) return hop_set_err(c, HOP_ERR_ARG, "hop_intra_cu_device_classes: bad argument");
   if (!c->have_orig) return hop_set_err(c, HOP_ERR_STATE, "hop_intra_cu_device_classes: hop_upload_orig has not been called");
   if (n_classes == 0) return HOP_OK;
-  return intra_classes_issue(c, n_classes, classes, d_ctx_in, d_cu_ctx_in);
+  return run_on_lanes(c, n_classes, "hop_intra_cu_device_classes", [&](int i) { return intra_candidate_chain(c, classes[i], d_ctx_in, d_cu_ctx_in); });
 }
 
 static int inter_candidate_chain(hop_ctx* c, const hop_inter_class& k, const hop_cabac_ctx* d_ctx_in, const hop_cabac_cu_ctx* d_cu_ctx_in) {
@@ -1331,10 +1130,9 @@ static int inter_candidate_chain(hop_ctx* c, const hop_inter_class& k, const hop
   if (k.n == 0) return HOP_OK;
   if (k.n <= c->walk_max && !getenv("HOP_WALK_NO_INTER")) {              // the RD spine's batches: one kernel per candidate (k_walk.inl)
     const hop_rqt_job* cls = &k.cls;
-    if (cls->log2_cu < 3 || cls->log2_cu > 6 || cls->log2_max_tu < 2 || cls->log2_max_tu > 5 || cls->log2_min_tu_in_cu < 2 || cls->log2_min_tu_in_cu > cls->log2_max_tu ||
-        cls->log2_cu - cls->log2_min_tu_in_cu > 3 || cls->log2_cu - cls->log2_max_tu > 1) return hop_set_err(c, HOP_ERR_ARG, "hop_inter_cu_device_classes: illegal CU class");
+    if (!rqt_class_ok(*cls)) return hop_set_err(c, HOP_ERR_ARG, "hop_inter_cu_device_classes: illegal CU class");
     if (!c->have_orig) return hop_set_err(c, HOP_ERR_STATE, "hop_inter_cu_device_classes: hop_upload_orig has not been called");
-    int r = hop_walk_reserve(c, hop_inter_walk_bytes(cls->log2_cu, cls->log2_max_tu, cls->log2_min_tu_in_cu, k.n)); if (r) return r;
+    int r = walk_reserve(c, hop_inter_walk_bytes(cls->log2_cu, cls->log2_max_tu, cls->log2_min_tu_in_cu, k.n)); if (r) return r;
     return hop_launch_inter_walk(c, cls, k.n, k.d_jobs, k.d_syntax, d_ctx_in, d_cu_ctx_in, k.d_results, k.d_coef, k.d_ctx_after, k.d_finals, k.d_bits, k.d_skipped, k.d_cost, k.d_ctx_out,
                                  k.d_cu_ctx_out, c->walk_buf, c->walk_bytes);
   }
@@ -1348,59 +1146,7 @@ int hop_inter_cu_device_classes(hop_ctx* c, int n_classes, const hop_inter_class
   if (!c || n_classes < 0 || (n_classes && (!classes || !d_ctx_in || !d_cu_ctx_in))) return hop_set_err(c, HOP_ERR_ARG, "hop_inter_cu_device_classes: bad argument");
   if (!c->have_orig) return hop_set_err(c, HOP_ERR_STATE, "hop_inter_cu_device_classes: hop_upload_orig has not been called");
   if (n_classes == 0) return HOP_OK;
-  auto issue = [&]() -> int {
-    // only the lanes this call uses take part
-    const int n_fork = std::min(n_classes, HOP_MAX_LANES) - 1;
-    if (n_fork > 0) HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
-    for (int k = 0; k < n_fork; k++) HIPCHK(c, hipStreamWaitEvent(c->xstream[k], c->ev_fork, 0));
-    bool used[HOP_MAX_LANES - 1] = { false, false, false };
-    int rc = HOP_OK;
-    for (int i = 0; i < n_classes && rc == HOP_OK; i++) {
-      const int lane = i % HOP_MAX_LANES;
-      if (lane == 0) { rc = inter_candidate_chain(c, classes[i], d_ctx_in, d_cu_ctx_in); continue; }
-      const int k = lane - 1;
-      std::swap(c->stream, c->xstream[k]); std::swap(c->scratch, c->xscratch[k]); std::swap(c->scratch_bytes, c->xscratch_bytes[k]);
-      std::swap(c->rqt_buf, c->xrqt_buf[k]); std::swap(c->rqt_bytes, c->xrqt_bytes[k]); std::swap(c->walk_buf, c->xwalk_buf[k]); std::swap(c->walk_bytes, c->xwalk_bytes[k]);
-      rc = inter_candidate_chain(c, classes[i], d_ctx_in, d_cu_ctx_in);
-      std::swap(c->stream, c->xstream[k]); std::swap(c->scratch, c->xscratch[k]); std::swap(c->scratch_bytes, c->xscratch_bytes[k]);
-      std::swap(c->rqt_buf, c->xrqt_buf[k]); std::swap(c->rqt_bytes, c->xrqt_bytes[k]); std::swap(c->walk_buf, c->xwalk_buf[k]); std::swap(c->walk_bytes, c->xwalk_bytes[k]);
-      used[k] = true;
-    }
-    for (int k = 0; k < HOP_MAX_LANES - 1; k++) {
-      if (!used[k]) continue;
-      hipError_t e = hipEventRecord(c->ev_join[k], c->xstream[k]);
-      if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, c->ev_join[k], 0);
-      if (e != hipSuccess && rc == HOP_OK) rc = hop_set_err(c, HOP_ERR_DEVICE, "hop_inter_cu_device_classes: stream join: %s", hipGetErrorString(e));
-    }
-    return rc;
-  };
-  return issue();
-}
-
-static int intra_classes_issue(hop_ctx* c, int n_classes, const hop_intra_class* classes, const hop_cabac_ctx* d_ctx_in, const hop_cabac_cu_ctx* d_cu_ctx_in) {
-  const int n_fork = std::min(n_classes, HOP_MAX_LANES) - 1;            // only the lanes this call uses (see hop_inter_cu_device_classes)
-  if (n_fork > 0) HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
-  for (int k = 0; k < n_fork; k++) HIPCHK(c, hipStreamWaitEvent(c->xstream[k], c->ev_fork, 0));
-  bool used[HOP_MAX_LANES - 1] = { false, false, false };
-  int rc = HOP_OK;
-  for (int i = 0; i < n_classes && rc == HOP_OK; i++) {
-    const int lane = i % HOP_MAX_LANES;
-    if (lane == 0) { rc = intra_candidate_chain(c, classes[i], d_ctx_in, d_cu_ctx_in); continue; }
-    const int k = lane - 1;
-    std::swap(c->stream, c->xstream[k]); std::swap(c->scratch, c->xscratch[k]); std::swap(c->scratch_bytes, c->xscratch_bytes[k]);
-    std::swap(c->rqt_buf, c->xrqt_buf[k]); std::swap(c->rqt_bytes, c->xrqt_bytes[k]); std::swap(c->walk_buf, c->xwalk_buf[k]); std::swap(c->walk_bytes, c->xwalk_bytes[k]);
-    rc = intra_candidate_chain(c, classes[i], d_ctx_in, d_cu_ctx_in);
-    std::swap(c->stream, c->xstream[k]); std::swap(c->scratch, c->xscratch[k]); std::swap(c->scratch_bytes, c->xscratch_bytes[k]);
-    std::swap(c->rqt_buf, c->xrqt_buf[k]); std::swap(c->rqt_bytes, c->xrqt_bytes[k]); std::swap(c->walk_buf, c->xwalk_buf[k]); std::swap(c->walk_bytes, c->xwalk_bytes[k]);
-    used[k] = true;
-  }
-  for (int k = 0; k < HOP_MAX_LANES - 1; k++) {
-    if (!used[k]) continue;
-    hipError_t e = hipEventRecord(c->ev_join[k], c->xstream[k]);
-    if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, c->ev_join[k], 0);
-    if (e != hipSuccess && rc == HOP_OK) rc = hop_set_err(c, HOP_ERR_DEVICE, "hop_intra_cu_device_classes: stream join: %s", hipGetErrorString(e));
-  }
-  return rc;
+  return run_on_lanes(c, n_classes, "hop_inter_cu_device_classes", [&](int i) { return inter_candidate_chain(c, classes[i], d_ctx_in, d_cu_ctx_in); });
 }
 
 int hop_inter_cu_bits_device(hop_ctx* c, int n, const hop_rqt_job* d_jobs, const hop_rqt_job* cls, const hop_cu_syntax* d_syntax, const hop_rqt_result* d_results, const int32_t* d_coef,
@@ -1408,8 +1154,7 @@ int hop_inter_cu_bits_device(hop_ctx* c, int n, const hop_rqt_job* d_jobs, const
                              hop_cabac_cu_ctx* d_cu_ctx_out) {
   if (!c || n < 0 || !cls || (n && (!d_jobs || !d_syntax || !d_results || !d_coef || !d_ctx_in || !d_cu_ctx_in || !d_bits || !d_skipped)))
     return hop_set_err(c, HOP_ERR_ARG, "hop_inter_cu_bits_device: bad argument");
-  if (cls->log2_cu < 3 || cls->log2_cu > 6 || cls->log2_max_tu < 2 || cls->log2_max_tu > 5 || cls->log2_min_tu_in_cu < 2 || cls->log2_min_tu_in_cu > cls->log2_max_tu ||
-      cls->log2_cu - cls->log2_min_tu_in_cu > 3 || cls->log2_cu - cls->log2_max_tu > 1) return hop_set_err(c, HOP_ERR_ARG, "hop_inter_cu_bits_device: illegal CU class");
+  if (!rqt_class_ok(*cls)) return hop_set_err(c, HOP_ERR_ARG, "hop_inter_cu_bits_device: illegal CU class");
   if (n == 0) return HOP_OK;
   return hop_launch_cu_bits(c, cls->log2_cu, cls->log2_max_tu, cls->log2_min_tu_in_cu, cls->inter_split_flag ? 1 : 0, cls->sign_hide ? 1 : 0, cls->use_ts ? 1 : 0, n, d_jobs, d_syntax,
                             d_results, d_coef, d_ctx_in, d_cu_ctx_in, d_bits, d_skipped, d_ctx_out, d_cu_ctx_out);
@@ -1422,56 +1167,34 @@ int hop_inter_cu_bits(hop_ctx* c, int n, const hop_rqt_job* jobs, const hop_cu_s
   std::vector<size_t> coff(n + 1, 0);
   for (int i = 0; i < n; i++) {
     const hop_rqt_job& j = jobs[i]; const hop_cu_syntax& y = syntax[i];
-    bool ok = j.log2_cu >= 3 && j.log2_cu <= 6 && j.ctx_index >= 0 && j.ctx_index < n_ctx && j.log2_max_tu >= 2 && j.log2_max_tu <= 5 && j.log2_min_tu_in_cu >= 2 &&
-              j.log2_min_tu_in_cu <= j.log2_max_tu && j.log2_cu - j.log2_min_tu_in_cu <= 3 && j.log2_cu - j.log2_max_tu <= 1 && y.part_size >= 0 && y.part_size <= 7 &&
+    bool ok = rqt_class_ok(j) && j.ctx_index >= 0 && j.ctx_index < n_ctx && y.part_size >= 0 && y.part_size <= 7 &&
               y.n_pu == (y.part_size == 0 ? 1 : y.part_size == 3 ? 4 : 2) && y.skip_ctx >= 0 && y.skip_ctx <= 2 && y.max_merge_cand >= 1 && y.max_merge_cand <= 5;
     for (int p = 0; p < y.n_pu && ok; p++) ok = y.pu[p].merge_flag ? (y.pu[p].merge_idx >= 0 && y.pu[p].merge_idx < 5) : (y.pu[p].mvp_idx >= 0 && y.pu[p].mvp_idx <= 1);
     if (!ok) return hop_set_err(c, HOP_ERR_ARG, "CU bits job %d: illegal CU class / syntax elements / snapshot", i);
-    coff[i + 1] = coff[i] + (((size_t)3 << (2 * j.log2_cu)) >> 1);
+    coff[i + 1] = coff[i] + cu_coeffs(j.log2_cu);
   }
-  for (int k = 0; k < n_ctx; k++) {
-    for (int i = 0; i < 150; i++) if (ctx_in[k].state[i] > 127) return hop_set_err(c, HOP_ERR_ARG, "context snapshot %d: state %d out of range", k, i);
-    for (int i = 0; i < 19; i++) if (cu_ctx_in[k].state[i] > 127) return hop_set_err(c, HOP_ERR_ARG, "CU context snapshot %d: state %d out of range", k, i);
-  }
-  std::vector<char> done(n, 0);
-  for (int first = 0; first < n; first++) {
-    if (done[first]) continue;
-    const hop_rqt_job& f = jobs[first];
-    std::vector<int> idx; std::vector<hop_rqt_job> cls; std::vector<hop_cu_syntax> sy; std::vector<hop_rqt_result> rr;
-    for (int i = first; i < n; i++) {
-      const hop_rqt_job& j = jobs[i];
-      if (!done[i] && j.log2_cu == f.log2_cu && j.log2_max_tu == f.log2_max_tu && j.log2_min_tu_in_cu == f.log2_min_tu_in_cu && !j.inter_split_flag == !f.inter_split_flag &&
-          !j.sign_hide == !f.sign_hide && !j.use_ts == !f.use_ts) { done[i] = 1; idx.push_back(i); cls.push_back(j); sy.push_back(syntax[i]); rr.push_back(results[i]); }
-    }
-    const int m = (int)idx.size();
-    const size_t cu3 = ((size_t)3 << (2 * f.log2_cu)) / 2;
-    std::vector<int32_t> co((size_t)m * cu3);
-    for (int t = 0; t < m; t++) memcpy(co.data() + (size_t)t * cu3, coef + coff[idx[t]], cu3 * 4);
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_j = 0, o_y = al((size_t)m * sizeof(hop_rqt_job)), o_r = al(o_y + (size_t)m * sizeof(hop_cu_syntax)), o_o = al(o_r + (size_t)m * sizeof(hop_rqt_result));
-    const size_t o_c = al(o_o + (size_t)m * cu3 * 4), o_u = al(o_c + (size_t)n_ctx * sizeof(hop_cabac_ctx)), o_b = al(o_u + (size_t)n_ctx * sizeof(hop_cabac_cu_ctx));
-    const size_t o_s = al(o_b + (size_t)m * 4), o_x = al(o_s + (size_t)m * 4), o_v = al(o_x + (size_t)m * sizeof(hop_cabac_ctx)), o_e = al(o_v + (size_t)m * sizeof(hop_cabac_cu_ctx));
-    void* st; int r = hop_stage(c, o_e + 256, &st); if (r) return r;
-    char* b = (char*)st;
-    HIPCHK(c, hipMemcpyAsync(b + o_j, cls.data(), (size_t)m * sizeof(hop_rqt_job), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b + o_y, sy.data(), (size_t)m * sizeof(hop_cu_syntax), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b + o_r, rr.data(), (size_t)m * sizeof(hop_rqt_result), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b + o_o, co.data(), (size_t)m * cu3 * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b + o_c, ctx_in, (size_t)n_ctx * sizeof(hop_cabac_ctx), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b + o_u, cu_ctx_in, (size_t)n_ctx * sizeof(hop_cabac_cu_ctx), hipMemcpyHostToDevice, c->stream));
-    r = hop_launch_cu_bits(c, f.log2_cu, f.log2_max_tu, f.log2_min_tu_in_cu, f.inter_split_flag ? 1 : 0, f.sign_hide ? 1 : 0, f.use_ts ? 1 : 0, m, (const hop_rqt_job*)(b + o_j),
-                           (const hop_cu_syntax*)(b + o_y), (const hop_rqt_result*)(b + o_r), (const int32_t*)(b + o_o), (const hop_cabac_ctx*)(b + o_c),
-                           (const hop_cabac_cu_ctx*)(b + o_u), (uint32_t*)(b + o_b), (uint32_t*)(b + o_s), (hop_cabac_ctx*)(b + o_x), (hop_cabac_cu_ctx*)(b + o_v));
+  if (!ctx_states_ok(c, n_ctx, ctx_in, cu_ctx_in)) return HOP_ERR_ARG;
+  auto same = [&](int p, int q) { return same_tree(jobs[p], jobs[q]) && !jobs[p].inter_split_flag == !jobs[q].inter_split_flag && !jobs[p].sign_hide == !jobs[q].sign_hide; };
+  return for_each_class(n, same, [&](const std::vector<int>& idx) {
+    const hop_rqt_job& f = jobs[idx[0]];
+    const size_t m = idx.size(), cu3 = cu_coeffs(f.log2_cu);
+    const std::vector<hop_rqt_job> cls = gather(jobs, idx); const std::vector<hop_cu_syntax> sy = gather(syntax, idx); const std::vector<hop_rqt_result> rr = gather(results, idx);
+    const std::vector<int32_t> co = gather(coef, idx, cu3, coff.data());
+    stage_arena a(c);
+    auto dj = a.in(cls.data(), m); auto dy = a.in(sy.data(), m); auto dr = a.in(rr.data(), m); auto d_co = a.in(co.data(), m * cu3); auto dc = a.in(ctx_in, n_ctx); auto du = a.in(cu_ctx_in, n_ctx);
+    auto db = a.out<uint32_t>(m); auto ds = a.out<uint32_t>(m); auto dx = a.out<hop_cabac_ctx>(m); auto dv = a.out<hop_cabac_cu_ctx>(m);
+    a.end_mark();
+    int r = a.commit(256); if (r) return r;
+    r = hop_launch_cu_bits(c, f.log2_cu, f.log2_max_tu, f.log2_min_tu_in_cu, f.inter_split_flag ? 1 : 0, f.sign_hide ? 1 : 0, f.use_ts ? 1 : 0, (int)m, a[dj], a[dy], a[dr], a[d_co], a[dc], a[du],
+                           a[db], a[ds], a[dx], a[dv]);
     if (r) return r;
     std::vector<uint32_t> bb(m), ss(m); std::vector<hop_cabac_ctx> cx(m); std::vector<hop_cabac_cu_ctx> cv(m);
-    HIPCHK(c, hipMemcpyAsync(bb.data(), b + o_b, (size_t)m * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(ss.data(), b + o_s, (size_t)m * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(cx.data(), b + o_x, (size_t)m * sizeof(hop_cabac_ctx), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(cv.data(), b + o_v, (size_t)m * sizeof(hop_cabac_cu_ctx), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int t = 0; t < m; t++) { bits[idx[t]] = bb[t]; skipped[idx[t]] = ss[t]; if (ctx_out) ctx_out[idx[t]] = cx[t]; if (cu_ctx_out) cu_ctx_out[idx[t]] = cv[t]; }
-  }
-  return HOP_OK;
+    if ((r = a.download(bb.data(), db)) || (r = a.download(ss.data(), ds)) || (r = a.download(cx.data(), dx)) || (r = a.download(cv.data(), dv)) || (r = a.sync())) return r;
+    scatter(bits, idx, bb.data()); scatter(skipped, idx, ss.data());
+    if (ctx_out) scatter(ctx_out, idx, cx.data());
+    if (cu_ctx_out) scatter(cu_ctx_out, idx, cv.data());
+    return (int)HOP_OK;
+  });
 }
 
 int hop_tu_rd(hop_ctx* c, int n, const hop_tu_rd_job* jobs, int n_ctx, const hop_cabac_ctx* ctx_in, hop_tu_rd_result* results, int32_t* levels_out) {
@@ -1491,74 +1214,42 @@ int hop_tu_rd(hop_ctx* c, int n, const hop_tu_rd_job* jobs, int n_ctx, const hop
       return hop_set_err(c, HOP_ERR_ARG, "TU RD job %d: illegal transform unit / snapshot / parameters", i);
     offs[i] = (int64_t)tot; tot += (size_t)N * N;
   }
-  for (int k = 0; k < n_ctx; k++) for (int i = 0; i < 150; i++) if (ctx_in[k].state[i] > 127) return hop_set_err(c, HOP_ERR_ARG, "context snapshot %d: state %d out of range", k, i);
-  const size_t bj = (size_t)n * sizeof(hop_tu_rd_job), o_c = (bj + 255) & ~(size_t)255, bc = (size_t)n_ctx * sizeof(hop_cabac_ctx);
-  const size_t o_o = (o_c + bc + 255) & ~(size_t)255, o_l = (o_o + (size_t)n * 8 + 255) & ~(size_t)255, o_r = (o_l + tot * 4 + 255) & ~(size_t)255;
-  void* st; int r = hop_stage(c, o_r + (size_t)n * sizeof(hop_tu_rd_result) + 256, &st); if (r) return r;
-  char* b = (char*)st;
-  HIPCHK(c, hipMemcpyAsync(b, jobs, bj, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(b + o_c, ctx_in, bc, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(b + o_o, offs.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-  r = hop_launch_tu_rd(c, n, (const hop_tu_rd_job*)b, (const hop_cabac_ctx*)(b + o_c), (const int64_t*)(b + o_o), tot, (int32_t*)(b + o_l), (hop_tu_rd_result*)(b + o_r), 0);
-  if (r) return r;
-  HIPCHK(c, hipMemcpyAsync(results, b + o_r, (size_t)n * sizeof(hop_tu_rd_result), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(levels_out, b + o_l, tot * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return HOP_OK;
+  if (!ctx_states_ok(c, n_ctx, ctx_in, nullptr)) return HOP_ERR_ARG;
+  stage_arena a(c);
+  auto dj = a.in(jobs, n); auto dc = a.in(ctx_in, n_ctx); auto d_off = a.in(offs.data(), n); auto dl = a.out<int32_t>(tot); auto dr = a.out<hop_tu_rd_result>(n);
+  int r = a.commit(256); if (r) return r;
+  r = hop_launch_tu_rd(c, n, a[dj], a[dc], a[d_off], tot, a[dl], a[dr], 0); if (r) return r;
+  if ((r = a.download(results, dr)) || (r = a.download(levels_out, dl))) return r;
+  return a.sync();
 }
 
 int hop_intra_pred(hop_ctx* c, int n, const hop_intra_job* jobs, const int32_t* modes) {
   if (!c || n < 0 || (n && (!jobs || !modes))) return hop_set_err(c, HOP_ERR_ARG, "hop_intra_pred: bad argument");
   if (n == 0) return HOP_OK;
+  int u = 0;
   for (int i = 0; i < n; i++) {
-    const hop_intra_job& j = jobs[i];
-    const int N = j.size;
-    if (!(N == 4 || N == 8 || N == 16 || N == 32 || N == 64) || j.x < 0 || j.y < 0 || (j.x & 3) || (j.y & 3) || j.x + N > c->pic_w || j.y + N > c->pic_h || modes[i] < 0 || modes[i] > 34)
-      return hop_set_err(c, HOP_ERR_ARG, "intra pred job %d: illegal block or mode", i);
-    const int U = N / 4;
-    for (int u = 0; u < 4 * U + 1; u++) if (j.flags[u]) {
-      bool ok;
-      if (u < 2 * U) ok = j.x > 0 && j.y + 4 * (2 * U - 1 - u) + 4 <= c->pic_h;
-      else if (u == 2 * U) ok = j.x > 0 && j.y > 0;
-      else ok = j.y > 0 && j.x + 4 * (u - 2 * U - 1) + 4 <= c->pic_w;
-      if (!ok) return hop_set_err(c, HOP_ERR_ARG, "intra pred job %d: neighbour unit %d flagged available but outside the picture", i, u);
-    }
+    if (!intra_block_ok(c, jobs[i], 0) || modes[i] < 0 || modes[i] > 34) return hop_set_err(c, HOP_ERR_ARG, "intra pred job %d: illegal block or mode", i);
+    if (!intra_neighbours_ok(c, jobs[i], 0, &u)) return hop_set_err(c, HOP_ERR_ARG, "intra pred job %d: neighbour unit %d flagged available but outside the picture", i, u);
   }
-  const size_t bj = (size_t)n * sizeof(hop_intra_job), o_m = (bj + 255) & ~(size_t)255;
-  void* st; int r = hop_stage(c, o_m + (size_t)n * 4 + 256, &st); if (r) return r;
-  char* b = (char*)st;
-  HIPCHK(c, hipMemcpyAsync(b, jobs, bj, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(b + o_m, modes, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-  r = hop_launch_intra_pred(c, n, (const hop_intra_job*)b, (const int32_t*)(b + o_m)); if (r) return r;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return HOP_OK;
+  stage_arena a(c);
+  auto dj = a.in(jobs, n); auto dm = a.in(modes, n);
+  int r = a.commit(256); if (r) return r;
+  r = hop_launch_intra_pred(c, n, a[dj], a[dm]); if (r) return r;
+  return a.sync();
 }
 int hop_intra_pred_chroma(hop_ctx* c, int n, const hop_intra_job* jobs, const int32_t* modes) {
   if (!c || n < 0 || (n && (!jobs || !modes))) return hop_set_err(c, HOP_ERR_ARG, "hop_intra_pred_chroma: bad argument");
   if (n == 0) return HOP_OK;
-  const int cw = c->pic_w >> 1, ch = c->pic_h >> 1;
+  int u = 0;
   for (int i = 0; i < n; i++) {
-    const hop_intra_job& j = jobs[i];
-    const int N = j.size, x = j.x >> 1, y = j.y >> 1;
-    if (!(N == 4 || N == 8 || N == 16 || N == 32) || j.x < 0 || j.y < 0 || (j.x & 7) || (j.y & 7) || x + N > cw || y + N > ch || modes[i] < 0 || modes[i] > 34)
-      return hop_set_err(c, HOP_ERR_ARG, "chroma intra pred job %d: illegal block or mode", i);
-    const int U = N / 2;
-    for (int u = 0; u < 4 * U + 1; u++) if (j.flags[u]) {
-      bool ok;
-      if (u < 2 * U) ok = x > 0 && y + 2 * (2 * U - 1 - u) + 2 <= ch;
-      else if (u == 2 * U) ok = x > 0 && y > 0;
-      else ok = y > 0 && x + 2 * (u - 2 * U - 1) + 2 <= cw;
-      if (!ok) return hop_set_err(c, HOP_ERR_ARG, "chroma intra pred job %d: neighbour unit %d flagged available but outside the picture", i, u);
-    }
+    if (!intra_block_ok(c, jobs[i], 1) || modes[i] < 0 || modes[i] > 34) return hop_set_err(c, HOP_ERR_ARG, "chroma intra pred job %d: illegal block or mode", i);
+    if (!intra_neighbours_ok(c, jobs[i], 1, &u)) return hop_set_err(c, HOP_ERR_ARG, "chroma intra pred job %d: neighbour unit %d flagged available but outside the picture", i, u);
   }
-  const size_t bj = (size_t)n * sizeof(hop_intra_job), o_m = (bj + 255) & ~(size_t)255;
-  void* st; int r = hop_stage(c, o_m + (size_t)n * 4 + 256, &st); if (r) return r;
-  char* b = (char*)st;
-  HIPCHK(c, hipMemcpyAsync(b, jobs, bj, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(b + o_m, modes, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-  r = hop_launch_intra_pred_chroma(c, n, (const hop_intra_job*)b, (const int32_t*)(b + o_m)); if (r) return r;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return HOP_OK;
+  stage_arena a(c);
+  auto dj = a.in(jobs, n); auto dm = a.in(modes, n);
+  int r = a.commit(256); if (r) return r;
+  r = hop_launch_intra_pred_chroma(c, n, a[dj], a[dm]); if (r) return r;
+  return a.sync();
 }
 int hop_intra_pred_chroma_device(hop_ctx* c, int n, const hop_intra_job* d_jobs, const int32_t* d_modes) {
   if (!c || n < 0 || (n && (!d_jobs || !d_modes))) return hop_set_err(c, HOP_ERR_ARG, "hop_intra_pred_chroma_device: bad argument");
@@ -1585,14 +1276,12 @@ int hop_distortion(hop_ctx* c, int n, const hop_dist_job* jobs, uint32_t* out) {
     if (j.comp < 0 || j.comp > 2 || j.kind < 0 || j.kind > 2 || j.x < 0 || j.y < 0 || j.w <= 0 || j.h <= 0 || (j.w & 3) || (j.h & 3) || j.x + j.w > c->pic_w || j.y + j.h > c->pic_h)
       return hop_set_err(c, HOP_ERR_ARG, "dist job %d: bad rectangle/kind", i);
   }
-  size_t bj = (size_t)n * sizeof(hop_dist_job), o_o = (bj + 255) & ~(size_t)255;
-  void* st; int r = hop_stage(c, o_o + (size_t)n * 4, &st); if (r) return r;
-  char* b = (char*)st;
-  HIPCHK(c, hipMemcpyAsync(b, jobs, bj, hipMemcpyHostToDevice, c->stream));
-  r = hop_launch_dist(c, n, (const hop_dist_job*)b, (uint32_t*)(b + o_o)); if (r) return r;
-  HIPCHK(c, hipMemcpyAsync(out, b + o_o, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return HOP_OK;
+  stage_arena a(c);
+  auto dj = a.in(jobs, n); auto d_o = a.out<uint32_t>(n);
+  int r = a.commit(0); if (r) return r;
+  r = hop_launch_dist(c, n, a[dj], a[d_o]); if (r) return r;
+  r = a.download(out, d_o); if (r) return r;
+  return a.sync();
 }
 
 } // extern "C"

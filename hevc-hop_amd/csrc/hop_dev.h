@@ -15,13 +15,20 @@
 #define HOP_GUARD_ROWS 64
 #define HOP_MAX_LANES 4
 
-struct hop_ctx {
+// What a lane of a context owns: a stream and the work areas of the kernels queued on it.  The context's own lane is its base (c->stream, c->scratch ...); hop_ctx.hip
+// runs independent chains of one call on the extra lanes by swapping one of them in (run_on_lanes).
+struct hop_lane {
+  hipStream_t stream;
+  void*  scratch; size_t scratch_bytes;   // grows on demand (never allocated inside a *_device call once sized)
+  void*  rqt_buf; size_t rqt_bytes;       // state of the residual-quadtree search (k_rqt.inl); separate from scratch, which its leaf pipeline uses
+  void*  walk_buf; size_t walk_bytes;     // work areas of the candidate walks (k_walk.inl): one kernel per candidate for the RD spine's small batches
+};
+struct hop_ctx : hop_lane {
   int pic_w, pic_h, bd_y, bd_c, device;
   int stride_y, stride_c;            // SS-ref strides (with margins)
   int slots;                         // hop_ctx_set_slots: the original, prediction and reconstruction pictures exist slots + 1 times, copy k at rows k * pic_h (0: once)
   int fused_leaf_max;                // hop_set_fused_leaf: leaf batches of up to this many TUs run as the one-kernel form (default 8192; 0 = always staged)
   int sub_h, sub_pitch;              // hop_ctx_set_stack: the picture is a stack of independent pictures of sub_h rows, origins sub_pitch rows apart (0, 0: one picture)
-  hipStream_t stream;
   // device pictures
   int16_t *org_y, *org_cb, *org_cr;  // original, pitch pic_w / pic_w/2, no margins
   int16_t *ss_alloc[3];              // allocations: HOP_GUARD_ROWS sentinel rows + padded plane + HOP_GUARD_ROWS
@@ -29,17 +36,11 @@ struct hop_ctx {
   int16_t *ss00[3];                  // sample (0,0) inside them
   int16_t *pred[3];                  // prediction picture, pitch pic_w / pic_w/2
   int16_t *rec[3];                   // reconstruction picture (TU round trip output, intra neighbours), same pitch
-  // scratch that grows on demand (never allocated inside a *_device call once sized)
-  void*  scratch; size_t scratch_bytes;
-  void*  stage;   size_t stage_bytes;   // staging for host-array entry points
-  void*  rqt_buf; size_t rqt_bytes;     // state of the residual-quadtree search (k_rqt.inl); separate from scratch, which its leaf pipeline uses
-  void*  walk_buf; size_t walk_bytes;   // work areas of the candidate walks (k_walk.inl): one kernel per candidate for the RD spine's small batches
-  void*  xwalk_buf[HOP_MAX_LANES - 1]; size_t xwalk_bytes[HOP_MAX_LANES - 1];   // ... of the extra lanes (classes of one call on separate streams)
+  void*  stage;   size_t stage_bytes;   // staging for host-array entry points; grows on demand
   int    walk_max;                      // batches of up to this many candidates take the walk kernels (HOP_WALK, default 4096; 0 = always the batch-step form)
-  void*  xrqt_buf[HOP_MAX_LANES - 1]; size_t xrqt_bytes[HOP_MAX_LANES - 1];
-  // extra lanes for hop_me_search_device: the parts of a batch run on separate streams so that one part's kernel tails
-  // and low-occupancy phases are filled by the other parts' kernels
-  hipStream_t xstream[HOP_MAX_LANES - 1]; void* xscratch[HOP_MAX_LANES - 1]; size_t xscratch_bytes[HOP_MAX_LANES - 1];
+  // extra lanes: the parts of a large hop_me_search_device batch and the classes of a *_device_classes call run on separate streams, so that one chain's kernel tails
+  // and low-occupancy phases are filled by the others' kernels
+  hop_lane xlane[HOP_MAX_LANES - 1];
   hipEvent_t ev_fork, ev_join[HOP_MAX_LANES - 1]; int lanes;   // HOP_LANES=1..4 (default 2)
   bool   have_orig;
   int32_t* entropy_bits;             // device: the 128 fractional-bit values of the CABAC states (ContextModel::m_entropyBits)
