@@ -909,7 +909,7 @@ int hop_intra_luma_search_device(hop_ctx* c, int n, const hop_rqt_job* d_jobs, c
   if (n == 0) return HOP_OK;
   int r = rqt_reserve(c, hop_intra_search_work_bytes(cls->log2_cu, n)); if (r) return r;
   return hop_launch_intra_search(c, cls->log2_cu, cls->log2_max_tu, cls->log2_min_tu_in_cu, cls->sign_hide ? 1 : 0, cls->use_ts ? 1 : 0, nxn, num_full_rd, n, d_jobs, d_syntax, d_opts,
-                                 d_sjobs, d_ctx_in, d_cu_ctx_in, d_sresults, d_results, d_coef_out, d_reco_out, c->rqt_buf, c->rqt_bytes, nullptr);
+                                 d_sjobs, d_ctx_in, d_cu_ctx_in, d_sresults, d_results, d_coef_out, d_reco_out, c->rqt_buf, c->rqt_bytes, nullptr, hop_intra_final_always());
 }
 
 int hop_intra_luma_search(hop_ctx* c, int n, const hop_rqt_job* jobs, const hop_intra_cu_syntax* syntax, const hop_intra_rqt_opt* opts, const hop_intra_search_job* sjobs,
@@ -1105,7 +1105,7 @@ static int intra_candidate_chain(hop_ctx* c, const hop_intra_class& k, const hop
   int r = rqt_reserve(c, std::max(hop_intra_search_work_bytes(cls->log2_cu, k.n), hop_intra_chroma_work_bytes(cls->log2_cu, k.n))); if (r) return r;
   const int sh = cls->sign_hide ? 1 : 0, ts = cls->use_ts ? 1 : 0;
   r = hop_launch_intra_search(c, cls->log2_cu, cls->log2_max_tu, cls->log2_min_tu_in_cu, sh, ts, nxn, k.num_full_rd, k.n, k.d_jobs, k.d_syntax, k.d_opts, k.d_sjobs, d_ctx_in, d_cu_ctx_in,
-                              k.d_sresults, k.d_results, k.d_coef, k.d_reco_y, c->rqt_buf, c->rqt_bytes, k.d_syntax_out);
+                              k.d_sresults, k.d_results, k.d_coef, k.d_reco_y, c->rqt_buf, c->rqt_bytes, k.d_syntax_out, hop_intra_final_always());
   if (r) return r;
   r = hop_launch_intra_chroma_search(c, cls->log2_cu, cls->log2_max_tu, cls->log2_min_tu_in_cu, sh, ts, k.n, k.d_jobs, k.d_syntax_out, k.d_opts, d_ctx_in, d_cu_ctx_in, k.d_results,
                                      k.d_cresults, k.d_coef, k.d_reco_c, c->rqt_buf, c->rqt_bytes, k.d_syntax_out);

@@ -18,6 +18,7 @@
 
 struct RqtClass { int log2_cu, log2_max_tu, log2_min_tu, inter_split, sign_hide, use_ts; };
 struct RqtNode { int part, d, log2, code_chroma, check_full, check_split, add_zero, ts_y, ts_c; };
+__host__ __device__ static inline bool rqt_intra_final_repeats(const RqtClass& k, int tr_depth0);   // (k_walk.inl, beside walk_rqt_node; hop_launch_intra_search asks it too)
 struct RqtWork {                                                      // per CU: what the reference keeps in locals of the recursion, by transform depth
   double   single_cost[4]; uint32_t single_bits[4], single_dist[4], abs_sum[4][3];
   double   sub_cost[5]; uint32_t sub_bits[5], sub_dist[5];            // what the children of depth d have added up (index 0: the CU's result)
@@ -1034,6 +1035,9 @@ int hop_launch_intra_rqt(hop_ctx* c, int log2_cu, int log2_max_tu, int log2_min_
 //                 state, k_is_keep (a better cost: arrays, levels and the PU's picture block kept aside - xSetIntraResultQT)
 //   k_is_commit   the kept arrays back, the decided block into the picture unless it is the last PU (:2603-2660), the cbf of an NxN CU combined (:2667-2685)
 // CUs with fewer candidates than the class maximum sit the spare passes out (empty slots in every batch of the pass).
+// Where the PU's root transform unit cannot split (rqt_intra_final_repeats: the 4x4 PUs of an NxN 8x8 CU), the pass for the best is the winner's candidate pass over again --
+// same direction, same entry state, same neighbours, same tree --, its cost is not strictly smaller and nothing of it is kept: it is left out, and k_is_commit puts the
+// last PU's block into the picture, where that pass would have left it.
 // =====================================================================================================================
 struct IsWork { double best_cost; uint32_t best_dist; int32_t best_mode; uint8_t tr[256], cbf[256], ts[256]; };
 
@@ -1101,12 +1105,14 @@ __global__ __launch_bounds__(64) void k_is_keep(RqtClass k, int pu, int nxn, int
 }
 
 // (every thread of the workgroup calls: barriers inside)
-__device__ static inline void is_commit_body(const int i, const int t, const int nt, const RqtClass& k, int pu, int nxn, const hop_rqt_job* jobs, const IsWork* work,
+// put_last: the last PU's block goes into the picture too.  The final pass leaves the winner's reconstruction there; where that pass was skipped as a repeat of the winner
+// (rqt_intra_final_repeats), the same samples come from reco_out
+__device__ static inline void is_commit_body(const int i, const int t, const int nt, const RqtClass& k, int pu, int nxn, int put_last, const hop_rqt_job* jobs, const IsWork* work,
                                              const hop_intra_modes_result* mres, hop_intra_cu_syntax* syn, hop_rqt_result* res, hop_intra_search_result* sres, int16_t* rec, int pitch,
                                              const int16_t* reco_out) {
   const int cu = 1 << k.log2_cu, parts = 1 << (2 * (k.log2_cu - 2)), q = parts >> (2 * nxn), part = pu * q, N = cu >> nxn, x0 = rqt_zx(part), y0 = rqt_zy(part), npu = nxn ? 4 : 1;
   for (int e = t; e < q; e += nt) { res[i].tr_idx[part + e] = work[i].tr[part + e]; res[i].cbf[0][part + e] = work[i].cbf[part + e]; res[i].tskip[0][part + e] = work[i].ts[part + e]; }
-  if (pu != npu - 1) {
+  if (pu != npu - 1 || put_last) {
     int16_t* pic = rec + (size_t)(jobs[i].y + y0) * pitch + jobs[i].x + x0;
     for (int e = t; e < N * N; e += nt) { const int rr = e / N, cc = e % N; pic[(size_t)rr * pitch + cc] = reco_out[(size_t)i * ((size_t)cu * cu) + (size_t)(y0 + rr) * cu + x0 + cc]; }
   }
@@ -1123,10 +1129,10 @@ __device__ static inline void is_commit_body(const int i, const int t, const int
     for (int e = t; e < parts; e += nt) res[i].cbf[0][e] |= (uint8_t)comb;
   }
 }
-__global__ __launch_bounds__(64) void k_is_commit(RqtClass k, int pu, int nxn, const hop_rqt_job* __restrict__ jobs, int n, const IsWork* __restrict__ work,
+__global__ __launch_bounds__(64) void k_is_commit(RqtClass k, int pu, int nxn, int put_last, const hop_rqt_job* __restrict__ jobs, int n, const IsWork* __restrict__ work,
                                                   const hop_intra_modes_result* __restrict__ mres, hop_intra_cu_syntax* __restrict__ syn, hop_rqt_result* __restrict__ res,
                                                   hop_intra_search_result* __restrict__ sres, int16_t* __restrict__ rec, int pitch, const int16_t* __restrict__ reco_out) {
-  is_commit_body(blockIdx.x, threadIdx.x, 64, k, pu, nxn, jobs, work, mres, syn, res, sres, rec, pitch, reco_out);
+  is_commit_body(blockIdx.x, threadIdx.x, 64, k, pu, nxn, put_last, jobs, work, mres, syn, res, sres, rec, pitch, reco_out);
 }
 
 size_t hop_intra_search_work_bytes(int log2_cu, int n) {
@@ -1135,12 +1141,18 @@ size_t hop_intra_search_work_bytes(int log2_cu, int n) {
                                                              sizeof(IsWork) + sizeof(hop_rqt_result) + (cu2 + (cu2 >> 1)) * 4 + 1) + 16 * 256;
 }
 
+// developer switch HOP_INTRA_FINAL_ALWAYS=1 (read per call: the tests flip it): the best mode goes through the full tree again for every PU, also where that pass can only
+// repeat the winner (rqt_intra_final_repeats).  The results do not depend on it
+int hop_intra_final_always() { const char* e = getenv("HOP_INTRA_FINAL_ALWAYS"); return (e && e[0] == '1') ? 1 : 0; }
+
 // one class of CUs: size, transform-tree limits / flags, partition (2Nx2N or NxN) and the candidate count of the PU size; buf = hop_intra_search_work_bytes
 int hop_launch_intra_search(hop_ctx* c, int log2_cu, int log2_max_tu, int log2_min_tu, int sign_hide, int use_ts, int nxn, int num_full_rd, int n, const hop_rqt_job* d_jobs,
                             const hop_intra_cu_syntax* d_syn_in, const hop_intra_rqt_opt* d_opt, const hop_intra_search_job* d_sj, const hop_cabac_ctx* d_ctx_in,
                             const hop_cabac_cu_ctx* d_cu_in, hop_intra_search_result* d_sres, hop_rqt_result* d_res, int32_t* d_coef_out, int16_t* d_reco_out, void* vbuf,
-                            size_t buf_bytes, hop_intra_cu_syntax* d_syn_out /* may be NULL: the syntax elements with the decided directions and their predictors */) {
+                            size_t buf_bytes, hop_intra_cu_syntax* d_syn_out /* may be NULL: the syntax elements with the decided directions and their predictors */,
+                            int final_always /* hop_intra_final_always() */) {
   RqtClass k; k.log2_cu = log2_cu; k.log2_max_tu = log2_max_tu; k.log2_min_tu = log2_min_tu; k.inter_split = 0; k.sign_hide = sign_hide; k.use_ts = use_ts;
+  const bool skip_final = !final_always && rqt_intra_final_repeats(k, nxn);   // the best mode's full tree is the tree it has been through: nothing of that pass would be kept
   auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
   const size_t cu2 = (size_t)1 << (2 * log2_cu), rq = al(hop_intra_rqt_work_bytes(log2_cu, n));
   char* buf = (char*)vbuf;
@@ -1167,12 +1179,13 @@ int hop_launch_intra_search(hop_ctx* c, int log2_cu, int log2_max_tu, int log2_m
     r = hop_launch_intra_modes(c, n, mj, satd, mres); if (r) return r;
     for (int pass = 0; pass <= n_max; pass++) {
       hipLaunchKernelGGL(k_is_pick, dim3(g256), dim3(256), 0, c->stream, pu, pass, n_max, n, mres, work, syn, active);
+      if (pass == n_max && skip_final) break;                           // (the pick stays: the decided direction into the syntax elements)
       r = hop_launch_intra_rqt(c, log2_cu, log2_max_tu, log2_min_tu, sign_hide, use_ts, nxn, pass < n_max ? 1 : 0, n, d_jobs, syn, d_opt, d_ctx_in, d_cu_in, tmp, coef_tmp, nullptr,
                                nullptr, buf, rq, active);
       if (r) return r;
       hipLaunchKernelGGL(k_is_keep, dim3(n), dim3(64), 0, c->stream, k, pu, nxn, pass, n_max, d_jobs, n, mres, syn, tmp, coef_tmp, c->rec[0], pitch, work, d_coef_out, d_reco_out);
     }
-    hipLaunchKernelGGL(k_is_commit, dim3(n), dim3(64), 0, c->stream, k, pu, nxn, d_jobs, n, work, mres, syn, d_res, d_sres, c->rec[0], pitch, d_reco_out);
+    hipLaunchKernelGGL(k_is_commit, dim3(n), dim3(64), 0, c->stream, k, pu, nxn, skip_final ? 1 : 0, d_jobs, n, work, mres, syn, d_res, d_sres, c->rec[0], pitch, d_reco_out);
   }
   if (d_syn_out) {
     e = hipMemcpyAsync(d_syn_out, syn, (size_t)n * sizeof(hop_intra_cu_syntax), hipMemcpyDeviceToDevice, c->stream);

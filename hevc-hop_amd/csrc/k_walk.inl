@@ -42,6 +42,14 @@ __device__ static inline RqtNode walk_rqt_node(const RqtClass& k, int parts, int
   nd.ts_c = (k.use_ts && nd.check_full && nd.code_chroma && (log2 == 2 || log2 == 3)) ? 1 : 0;
   return nd;
 }
+// estIntraPredQT sends the PU's best mode through the transform tree once more without bCheckFirst and keeps that result only if it costs strictly less.  bCheckFirst takes
+// the split away from a node that has check_full (walk_intra_rqt, Rec::go of hop_launch_intra_rqt); a root that has check_full and cannot split anyway (the 4x4 PUs of an
+// NxN 8x8 CU) is the same tree with and without it.  The pass for the best is then the winner's candidate pass over again -- the same direction from the same entry state,
+// neighbours and transform-skip alternative --, ends at the winner's cost bit for bit and leaves, besides nothing kept, the winner's block in the picture.
+__host__ __device__ static inline bool rqt_intra_final_repeats(const RqtClass& k, int tr_depth0) {
+  const int log2 = k.log2_cu - tr_depth0;                               // the PU's root node
+  return log2 <= k.log2_max_tu /* check_full */ && log2 <= k.log2_min_tu /* no check_split */;
+}
 
 // the inverse path in reconstruction mode over a candidate's table of nj jobs (hop_launch_tu_recon): the large transform units one after the other on the whole workgroup,
 // the 4x4 / 8x8 ones a wave each
@@ -216,7 +224,7 @@ int hop_launch_inter_walk(hop_ctx* c, const hop_rqt_job* cls, int n, const hop_r
 // tree has (the batch form visits every node a tree of the class can have and lets the CUs without a transform unit there sit the step out: the same work).
 // =====================================================================================================================
 struct IntraWalk {
-  RqtClass k; int n, nxn, num_full_rd, bd_y, bd_c; hop_pics pic;
+  RqtClass k; int n, nxn, num_full_rd, bd_y, bd_c, final_always /* HOP_INTRA_FINAL_ALWAYS=1 */; hop_pics pic;
   const hop_rqt_job* jobs; const hop_intra_cu_syntax* syn_in; const hop_intra_rqt_opt* opt; const hop_intra_search_job* sj; const hop_cabac_ctx* ctx_in; const hop_cabac_cu_ctx* cu_in;
   hop_intra_search_result* sres; hop_rqt_result* res; hop_intra_chroma_result* cres; int32_t* coef_out; int16_t* reco_y; int16_t* reco_c; hop_intra_cu_syntax* syn_out;
   uint32_t* dist; uint32_t* bits; double* cost; hop_cabac_ctx* ctx_out; hop_cabac_cu_ctx* cu_out;
@@ -307,15 +315,19 @@ __device__ static void iw_luma_prep(const IntraWalk& A, WalkShared& L, const int
   if (threadIdx.x == 0) intra_modes_body(i, A.mj, A.satd, A.mres);
   __syncthreads();
 }
-// the best mode again with the full tree, the better result kept, the decided PU into the picture (:2555-2660)
+// the best mode again with the full tree, the better result kept, the decided PU into the picture (:2555-2660).  Where that pass repeats the winner it is left out, and the
+// commit puts the last PU's block into the picture too, where the pass would have left it (`skip` is uniform over the grid: every barrier is reached by all or by none)
 __device__ static void iw_luma_final(const IntraWalk& A, WalkShared& L, CabacLds1& sh1, const int i, const int pu) {
   const int tid = threadIdx.x, n_max = A.num_full_rd + 2, pitch = A.pic.pic_w;
+  const bool skip = !A.final_always && rqt_intra_final_repeats(A.k, A.nxn);
   if (tid == 0) is_pick_body(i, pu, n_max, n_max, A.mres, A.iswork, A.syn, A.active);
   __syncthreads();
-  walk_intra_rqt(A, L, sh1, i, A.nxn, 0);
-  is_keep_body(i, tid, 256, A.k, pu, A.nxn, n_max, n_max, A.jobs, A.mres, A.syn, A.tmp, A.coef_tmp, A.rec_y, pitch, A.iswork, A.coef_out, A.reco_y);
-  __syncthreads();
-  is_commit_body(i, tid, 256, A.k, pu, A.nxn, A.jobs, A.iswork, A.mres, A.syn, A.res, A.sres, A.rec_y, pitch, A.reco_y);
+  if (!skip) {
+    walk_intra_rqt(A, L, sh1, i, A.nxn, 0);
+    is_keep_body(i, tid, 256, A.k, pu, A.nxn, n_max, n_max, A.jobs, A.mres, A.syn, A.tmp, A.coef_tmp, A.rec_y, pitch, A.iswork, A.coef_out, A.reco_y);
+    __syncthreads();
+  }
+  is_commit_body(i, tid, 256, A.k, pu, A.nxn, skip ? 1 : 0, A.jobs, A.iswork, A.mres, A.syn, A.res, A.sres, A.rec_y, pitch, A.reco_y);
   __syncthreads();
 }
 // one direction of estIntraPredChromaQT along the luma tree in A.res[i] (xRecurIntraChromaCodingQT :2130-2277), then the CU's chroma bits and cost (ic_bits)
@@ -476,7 +488,7 @@ __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_iw_cand(IntraWalk 
 }
 
 // the decisions over the candidate passes in their order (strict '<': the first of equal costs stays), the winner's arrays, levels and block kept (xSetIntraResultQT), then
-// the best mode again with the full tree and the PU's commit; the next PU's candidate list, or the chroma search's start
+// the best mode again with the full tree (unless that repeats the winner: iw_luma_final) and the PU's commit; the next PU's candidate list, or the chroma search's start
 __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_iw_pick(IntraWalk A, int pu) {
   __shared__ WalkShared L;
   __shared__ CabacLds1 sh1;
@@ -558,6 +570,11 @@ __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_iw_finish(IntraWal
     }
     const int16_t* pic = (comp == 1 ? B.rec_cb : B.rec_cr) + (ptrdiff_t)(jb.y >> 1) * pitch_c + (jb.x >> 1);
     for (int e = tid; e < (int)h2; e += 256) { const int rr = e / half, cc = e % half; A.reco_c[(size_t)i * 2 * h2 + (size_t)(comp - 1) * h2 + e] = pic[(ptrdiff_t)rr * pitch_c + cc]; }
+    // the picture keeps the LAST direction's block, as where the directions run one after the other in the picture itself (k_intra_walk, hop_launch_intra_chroma_search):
+    // every form of the chain leaves the context in the same state
+    const ptrdiff_t o4 = ((ptrdiff_t)(i * A.P + 4) * A.hbc + 1) * pitch_c + (jb.x >> 1), op = (ptrdiff_t)(jb.y >> 1) * pitch_c + (jb.x >> 1);
+    const int16_t* last = A.band_rec[comp] + o4; int16_t* out = comp == 1 ? A.rec_cb : A.rec_cr;
+    for (int e = tid; e < (int)h2; e += 256) { const int rr = e / half, cc = e % half; out[op + (ptrdiff_t)rr * pitch_c + cc] = last[(ptrdiff_t)rr * pitch_c + cc]; }
   }
   if (tid == 0) {
     const IcWork* w = A.icwork + v;
@@ -596,7 +613,7 @@ int hop_launch_intra_walk(hop_ctx* c, const hop_intra_class& q, const hop_cabac_
   const bool par = iw_parallel(c, k.log2_cu, n, q.num_full_rd);
   A.P = par ? iw_passes(q.num_full_rd) : 1; A.V = n * A.P;
   const size_t V = (size_t)A.V;
-  A.n = n; A.nxn = q.part_nxn ? 1 : 0; A.num_full_rd = q.num_full_rd; A.bd_y = c->bd_y; A.bd_c = c->bd_c; A.pic = hop_make_pics(c); A.pic_h = c->pic_h;
+  A.n = n; A.nxn = q.part_nxn ? 1 : 0; A.num_full_rd = q.num_full_rd; A.final_always = hop_intra_final_always(); A.bd_y = c->bd_y; A.bd_c = c->bd_c; A.pic = hop_make_pics(c); A.pic_h = c->pic_h;
   A.jobs = q.d_jobs; A.syn_in = q.d_syntax; A.opt = q.d_opts; A.sj = q.d_sjobs; A.ctx_in = d_ctx_in; A.cu_in = d_cu_in;
   A.sres = q.d_sresults; A.res = q.d_results; A.cres = q.d_cresults; A.coef_out = q.d_coef; A.reco_y = q.d_reco_y; A.reco_c = q.d_reco_c; A.syn_out = q.d_syntax_out;
   A.dist = q.d_dist; A.bits = q.d_bits; A.cost = q.d_cost; A.ctx_out = q.d_ctx_out; A.cu_out = q.d_cu_ctx_out;
