@@ -139,6 +139,17 @@ __device__ static inline int hopd_satd4x4_quad(int d, int lane) {
   for (int o = 1; o < 16; o <<= 1) s += __shfl_xor(s, o, 64);
   return (s + 1) >> 1;
 }
+
+// ---- a pointer's address space across a function call ----
+// A pointer that is a parameter of a non-inlined device function is generic: the compiler addresses it with flat_* instructions (which wait on both the vector-memory and
+// the LDS counter) and loses what the caller knew.  This gives it back where the callee's contract says the object is the caller's __shared__ one: every access through the result is
+// a ds_* instruction.  The value is unchanged.  (There is no such statement for HBM: a generic pointer to HBM stays flat_*, which costs the second counter, not a detour.)
+template <class T> __device__ static __forceinline__ T* hopd_lds(T* p) {
+#ifdef __HIP_DEVICE_COMPILE__
+  __builtin_assume(__builtin_amdgcn_is_shared((const void*)p));
+#endif
+  return p;
+}
 #endif // __HIPCC__
 
 // kernel launchers (each .hip file defines its own)

@@ -19,10 +19,31 @@ struct LeafShared {
   int32_t src[1024], lev[1024], ebits[128]; hop_estbits eb; uint8_t ctx[152]; double work[256 * RQ_WORK_PER_COEF / 8];
 };
 
+// The serial stages of one transform unit -- the bit-estimate table, RDOQ, the counted bits -- on the calling lane, as a FUNCTION OF ITS OWN.  Inlined into a candidate walk
+// they shared the walk's register budget with everything the walk keeps live around them, and the compiler spilled into the per-coefficient loops (a reload is a
+// vector-memory load on the dependent path).  As a function the loops get a register allocation of their own -- that of k_turd_fused_small, which holds the same code in 41
+// registers without a stack -- and the caller's live state is saved once around the call.  No barrier inside: the call may stand under `if (tid == 0)`.  L is the caller's
+// LeafShared / LeafSmallShared in LDS (hopd_lds: the loops address it with ds_* instructions, not flat_*), every other pointer is HBM.
+// MAXLOG2 = 5: a 32x32 unit's RDOQ work area is its slot of `work` in HBM; smaller units use L.work.
+template <class SH, int MAXLOG2>
+__device__ __noinline__ static void leaf_serial(SH* Lg, const int j, const int LOG2, const hop_tu_rd_job* jobs, const int n, const hop_cabac_ctx* ctx_in, const int64_t* coef_off,
+                                                uint32_t* as, unsigned long long* fr, hop_rdoq_job* rq, hop_coeff_bits_job* cb, char* work) {
+  SH& L = *hopd_lds(Lg);
+  turd_setup_body(j, jobs, n, ctx_in, coef_off, L.ebits, &L.eb, rq, cb, L.ctx);
+  const hop_rdoq_job rj = rq[j];
+  if (LOG2 == 2) rdoq_tu<2>(rj, &L.eb, L.scan, L.scanCG, L.cgSig, 1, L.src, L.lev, as + j, L.work, 1, 0);
+  else if (MAXLOG2 == 3 || LOG2 == 3) rdoq_tu<3>(rj, &L.eb, L.scan, L.scanCG, L.cgSig, 1, L.src, L.lev, as + j, L.work, 1, 0);
+  else if (LOG2 == 4) rdoq_tu<4>(rj, &L.eb, L.scan, L.scanCG, L.cgSig, 1, L.src, L.lev, as + j, L.work, 1, 0);
+  else rdoq_tu<5>(rj, &L.eb, L.scan, L.scanCG, L.cgSig, 1, L.src, L.lev, as + j, (double*)(work + (size_t)j * LEAF_WORK_PER_TU), 1, 0);
+  const hop_coeff_bits_job bj = cb[j];
+  fr[j] = cb_code_tu_at(L.cab, 0, L.lev, bj.log2_size, bj.comp != 0, bj.scan_idx, bj.sign_hide, bj.use_ts, bj.ts_flag, bj.cbf_ctx_plus1, L.scan, L.scanCG);
+}
+
 // one TU through all stages on the 256 threads of the calling workgroup (every thread calls; barriers inside)
-__device__ static void turd_fused_body(LeafShared& L, const int j, const hop_tu_rd_job* jobs, int n, hop_pics pic, const hop_cabac_ctx* ctx_in, const int64_t* coef_off,
+__device__ static void turd_fused_body(LeafShared& L_, const int j, const hop_tu_rd_job* jobs, int n, hop_pics pic, const hop_cabac_ctx* ctx_in, const int64_t* coef_off,
                                        const int32_t* entropy_bits, const uint16_t* scans, int32_t* coef, int32_t* levels, uint32_t* zs, uint32_t* ns, uint32_t* as,
                                        unsigned long long* fr, hop_rdoq_job* rq, hop_coeff_bits_job* cb, char* work, hop_tu_rd_result* res, int16_t* rec_y, int16_t* rec_cb, int16_t* rec_cr) {
+  LeafShared& L = *hopd_lds(&L_);                                     // (where the compiler makes this body a function of its own, &L_ arrives as a generic pointer)
   const int tid = threadIdx.x;
   const hop_tu_rd_job jb = jobs[j];
   if (jb.log2_size < 2 || jb.log2_size > 5) return;                   // an empty slot of a job table (k_rqt.inl); uniform over the workgroup
@@ -41,17 +62,7 @@ __device__ static void turd_fused_body(LeafShared& L, const int j, const hop_tu_
   { const uint8_t* st = ctx_in[jb.ctx_index].state; for (int i = tid; i < 152; i += 256) { const uint8_t v = st[i]; L.ctx[i] = v; L.cab.st[i][0] = v; } }
   for (int i = tid; i < 128; i += 256) L.ebits[i] = entropy_bits[i];
   __syncthreads();
-  if (tid == 0) {                                                     // the serial stages
-    turd_setup_body(j, jobs, n, ctx_in, coef_off, L.ebits, &L.eb, rq, cb, L.ctx);
-    const hop_rdoq_job rj = rq[j];
-    double* wd = LOG2 <= 4 ? L.work : (double*)(work + (size_t)j * LEAF_WORK_PER_TU);
-    if (LOG2 == 2) rdoq_tu<2>(rj, &L.eb, L.scan, L.scanCG, L.cgSig, 1, L.src, L.lev, as + j, wd, 1, 0);
-    else if (LOG2 == 3) rdoq_tu<3>(rj, &L.eb, L.scan, L.scanCG, L.cgSig, 1, L.src, L.lev, as + j, wd, 1, 0);
-    else if (LOG2 == 4) rdoq_tu<4>(rj, &L.eb, L.scan, L.scanCG, L.cgSig, 1, L.src, L.lev, as + j, wd, 1, 0);
-    else rdoq_tu<5>(rj, &L.eb, L.scan, L.scanCG, L.cgSig, 1, L.src, L.lev, as + j, wd, 1, 0);
-    const hop_coeff_bits_job bj = cb[j];
-    fr[j] = cb_code_tu_at(L.cab, 0, L.lev, bj.log2_size, bj.comp != 0, bj.scan_idx, bj.sign_hide, bj.use_ts, bj.ts_flag, bj.cbf_ctx_plus1, L.scan, L.scanCG);
-  }
+  if (tid == 0) leaf_serial<LeafShared, 5>(&L, j, LOG2, jobs, n, ctx_in, coef_off, as, fr, rq, cb, work);   // the serial stages
   __syncthreads();
   for (int i = tid; i < N2; i += 256) levels[off + i] = L.lev[i];
   __threadfence_block();
@@ -105,14 +116,7 @@ __device__ static __forceinline__ void turd_fused_small_wave_body(LeafSmallShare
     for (int i = lane; i < 128; i += 64) L.ebits[i] = entropy_bits[i];
   }
   __syncthreads();
-  if (live && lane == 0) {
-    turd_setup_body(j, jobs, n, ctx_in, coef_off, L.ebits, &L.eb, rq, cb, L.ctx);
-    const hop_rdoq_job rj = rq[j];
-    if (LOG2 == 2) rdoq_tu<2>(rj, &L.eb, L.scan, L.scanCG, L.cgSig, 1, L.src, L.lev, as + j, L.work, 1, 0);
-    else rdoq_tu<3>(rj, &L.eb, L.scan, L.scanCG, L.cgSig, 1, L.src, L.lev, as + j, L.work, 1, 0);
-    const hop_coeff_bits_job bj = cb[j];
-    fr[j] = cb_code_tu_at(L.cab, 0, L.lev, bj.log2_size, bj.comp != 0, bj.scan_idx, bj.sign_hide, bj.use_ts, bj.ts_flag, bj.cbf_ctx_plus1, L.scan, L.scanCG);
-  }
+  if (live && lane == 0) leaf_serial<LeafSmallShared, 3>(&L, j, LOG2, jobs, n, ctx_in, coef_off, as, fr, rq, cb, nullptr);
   __syncthreads();
   if (live && lane < N2) levels[off + lane] = L.lev[lane];
   __threadfence_block();

@@ -28,6 +28,9 @@ struct RqtWork {                                                      // per CU:
 // The kernels that walk a CU's coder serially take one LANE per CU (64 CUs per wave: batches of thousands of CUs) or, launched with one workgroup per CU (grid = n), one
 // WAVE per CU with lane 0 working: the lanes of a wave serialise wherever their CUs' paths differ, so a small batch -- the RD spine's, one CU per CTU in flight -- runs in
 // the time of ONE CU only when every CU has a wave of its own.  rqt_grid() picks the launch; the kernel tells the two apart by its grid.
+// CONTRACT of every `template <class LDS>` body of this file (and of cb_code_tu / cb_code_tu_at): `sh` must be a __shared__ object (CabacLds or CabacLds1).  The bodies the
+// compiler makes functions of their own say so to it (hopd_lds, hop_dev.h: an assumption, not a check) -- instantiated on a lane-private or HBM object they would be
+// miscompiled silently.
 #define RQT_LANE_OR_BLOCK(n_) const bool spread_ = (n_) > 1 && gridDim.x == (unsigned)(n_); if (spread_ && threadIdx.x) return; \
                               const int lane = spread_ ? 0 : (int)threadIdx.x, i = spread_ ? (int)blockIdx.x : (int)(blockIdx.x * 64 + threadIdx.x)
 // (a wave per CU needs one column of context states: CabacLds1, 204 bytes -- a compute unit then holds 32 such CUs instead of 12)
@@ -501,9 +504,11 @@ __device__ static unsigned long long cu_merge_index(LDS& sh, const int lane, con
 }
 
 template <class LDS>
-__device__ static void cu_bits_body(LDS& sh, const int lane, const int i, const RqtClass& k, const hop_rqt_job* jobs, const hop_cu_syntax* syn, const hop_rqt_result* res, const int32_t* coef,
+__device__ static void cu_bits_body(LDS& sh_, const int lane, const int i, const RqtClass& k_, const hop_rqt_job* jobs, const hop_cu_syntax* syn, const hop_rqt_result* res, const int32_t* coef,
                                     const hop_cabac_ctx* ctx_in, const hop_cabac_cu_ctx* cu_in, uint32_t* bits_out, uint32_t* skipped_out, hop_cabac_ctx* ctx_out, hop_cabac_cu_ctx* cu_out,
                                     const uint16_t* scans) {
+  LDS& sh = *hopd_lds(&sh_);                                         // (the coder states are in LDS wherever this body becomes a function of its own: ds_*, not flat_*)
+  const RqtClass k = k_;                                             // (and the class in registers, not behind a generic pointer into the caller's stack)
   const int ci = jobs[i].ctx_index;
   RQ_LOAD(ctx_in[ci]);
   for (int q = 0; q < 20; q++) sh.st[CUX + q][lane] = cu_in[ci].state[q];
@@ -637,8 +642,10 @@ __device__ static unsigned long long icu_dir(LDS& sh, const int lane, const int 
 
 // the counting itself, from the node (tr0, part0) downwards; levels either in the CU layout (cf) or in the layer buffers of the quadtree searches (layered, CU i)
 template <class LDS>
-__device__ __noinline__ static unsigned long long icu_count(LDS& sh, const int lane, const RqtClass& k, const hop_intra_cu_syntax& y, const int tr0, const int part0, const int b_luma,
+__device__ __noinline__ static unsigned long long icu_count(LDS& sh_, const int lane, const RqtClass& k_, const hop_intra_cu_syntax& y, const int tr0, const int part0, const int b_luma,
                                                const int b_chroma, const hop_rqt_result* r, const int32_t* cf, const int32_t* layered, const int i, const uint16_t* scans) {
+  LDS& sh = *hopd_lds(&sh_);                                         // a function of its own: sh arrives generic; said here, the coefficient loops of cb_code_tu reach the coder states with ds_*
+  const RqtClass k = k_;
   const int parts = 1 << (2 * (k.log2_cu - 2));
   const size_t cu2 = (size_t)1 << (2 * k.log2_cu);
   unsigned long long frac = 0;
@@ -1485,9 +1492,11 @@ int hop_launch_intra_chroma_search(hop_ctx* c, int log2_cu, int log2_max_tu, int
 // intra rules (the split of an NxN CU inferred, the luma cbf always coded, scans by direction).  One lane per CU; cost = calcRdCost(bits, distortion).
 // =====================================================================================================================
 template <class LDS>
-__device__ static void intra_cu_total_body(LDS& sh, const int lane, const int i, const RqtClass& k, const hop_rqt_job* jobs, const hop_intra_cu_syntax* syn, const hop_rqt_result* res,
+__device__ static void intra_cu_total_body(LDS& sh_, const int lane, const int i, const RqtClass& k_, const hop_rqt_job* jobs, const hop_intra_cu_syntax* syn, const hop_rqt_result* res,
                                            const int32_t* coef, const hop_cabac_ctx* ctx_in, const hop_cabac_cu_ctx* cu_in, const uint32_t* dist, uint32_t* bits_out, double* cost_out,
                                            hop_cabac_ctx* ctx_out, hop_cabac_cu_ctx* cu_out, const uint16_t* scans) {
+  LDS& sh = *hopd_lds(&sh_);
+  const RqtClass k = k_;
   const int ci = jobs[i].ctx_index;
   RQ_LOAD(ctx_in[ci]); IRQ_CU_LOAD(cu_in[ci]);
   const hop_intra_cu_syntax y = syn[i];

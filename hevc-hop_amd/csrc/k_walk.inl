@@ -11,11 +11,16 @@
 //                  syntax bits (xAddSymbolBitsInter :7779-7810) = cu_bits, calcRdCost
 // (the intra candidate walk follows the same scheme)
 
-// The walks are serial code on a few lanes: what they must not do is keep the short kernels of the spine's other requests (predictions, searches) off the compute units.
-// At the compiler's free choice they take 256 registers per lane -- two workgroups fill a compute unit's register files, and a few hundred candidates in flight the whole
-// chip; capped at 128 (four waves per SIMD) a compute unit holds four and still has room.
+// The walks are serial code on a few lanes; what bounds them is the latency of that lane's dependent instructions, so registers go to keeping its loops out of memory.
+// The figure is the occupancy the kernels are compiled for (amdgpu-waves-per-eu) and states what the compiler does: at 2 (a budget of 256 registers) the walks take 219 -
+// 256 registers and keep their coefficient loops free of spills; at 4 (128 registers) the compiler cannot get there -- 152 registers, occupancy 3, "failed to meet occupancy
+// target" on every walk kernel, reloads inside the per-coefficient loops (DESIGN.md section 4 has the table, section 5 the measurement).
+// What that costs: a walk workgroup is one wave per SIMD, so two of them fill a compute unit's register files and a compute unit that holds two runs no other kernel beside
+// them.  256 compute units hold 512 walk workgroups; a walk launch of the RD spine has one workgroup per candidate in flight (x candidate modes for k_iw_cand, x 5 for
+// k_iw_chroma), 25 - 500 per launch, and on four streams -- so the spine's short kernels (searches, predictions) find free compute units except beside the largest
+// launches, where they queue behind walk workgroups that end sooner than before.  DESIGN.md section 5 gives the request times of both kinds, before and after.
 #ifndef WALK_WAVES_PER_SIMD
-#define WALK_WAVES_PER_SIMD 4
+#define WALK_WAVES_PER_SIMD 2
 #endif
 struct InterWalk {
   RqtClass k; int n, bd_y, bd_c, wave_leaves; hop_pics pic;
@@ -169,6 +174,19 @@ __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_inter_walk(InterWa
   }
 }
 
+// HOP_WALK_FILL=<0..255> (developer switch, read per call): the walk launchers fill their work buffer with that byte, on the context's stream, before the launch.  Every word
+// of the buffer a walk reads it has written before, so results do not depend on the byte (tests/test_gpu_walk_codegen.py); unset: no fill, no cost.
+static int walk_fill(hop_ctx* c, void* vbuf, size_t buf_bytes) {
+  const char* e = getenv("HOP_WALK_FILL");
+  if (!e || !e[0]) return HOP_OK;
+  char* end = nullptr;
+  const long v = strtol(e, &end, 10);
+  if (end == e || *end || v < 0 || v > 255) return hop_set_err(c, HOP_ERR_STATE, "HOP_WALK_FILL=%s: a byte value 0..255", e);
+  hipError_t r = hipMemsetAsync(vbuf, (int)v, buf_bytes, c->stream);
+  if (r != hipSuccess) return hop_set_err(c, HOP_ERR_DEVICE, "walk fill: %s", hipGetErrorString(r));
+  return HOP_OK;
+}
+
 size_t hop_inter_walk_bytes(int log2_cu, int log2_max_tu, int log2_min_tu, int n) {
   const size_t cu2 = (size_t)1 << (2 * log2_cu), n_coeff = (size_t)n * (6 * cu2 + 48);
   int d0, d1; const int nj = rqt_jobs_per_cu(log2_cu, log2_max_tu, log2_min_tu, &d0, &d1);
@@ -208,6 +226,7 @@ int hop_launch_inter_walk(hop_ctx* c, const hop_rqt_job* cls, int n, const hop_r
   const size_t nt = (size_t)n * A.nj;
   A.ftuj = (hop_tu_rd_job*)take(nt * sizeof(hop_tu_rd_job)); A.foff = (int64_t*)take(nt * 8); A.faf = (uint32_t*)take(nt * 4); A.fsse = (uint32_t*)take(nt * 4);
   if (o > buf_bytes) return hop_set_err(c, HOP_ERR_STATE, "inter walk: work buffer too small");
+  { const int r = walk_fill(c, vbuf, buf_bytes); if (r) return r; }
   A.entropy_bits = hop_entropy_bits_device(c); A.scans = c->rdoq_scans; A.rec_y = c->rec[0]; A.rec_cb = c->rec[1]; A.rec_cr = c->rec[2];
   const int pr = hop_prof_begin(c, HOP_K_WALK_INTER + (k.log2_cu - 3), (uint64_t)n);
   hipLaunchKernelGGL(k_inter_walk, dim3(n), dim3(256), 0, c->stream, A);
@@ -248,16 +267,30 @@ struct IntraWalk {
   int16_t* band_pred[3]; int16_t* band_rec[3];
 };
 union WalkShared { LeafShared leaf; IntraShared intra; };
+// What differs between a candidate CU working in the picture and a virtual candidate working on its copies and in its band (k_iw_*): the walk bodies take these few members
+// from a view and everything else from the kernel's argument table A, which so stays in the kernel-argument segment (uniform loads).  A patched COPY of the table, which
+// this replaces, was a 600-byte stack object per lane -- A.root[d] is indexed at run time -- and every pointer loaded from it had lost its address space (flat_* accesses).
+struct IwView {
+  int n; const hop_rqt_job* jobs; hop_intra_cu_syntax* syn; hop_intra_cu_syntax* csyn; const hop_intra_rqt_opt* opt; hop_rqt_result* tmp; int32_t* coef_tmp; hop_rqt_result* res;
+  hop_pics pic; int16_t* rec_y; int16_t* rec_cb; int16_t* rec_cr;
+};
+__device__ static inline IwView iw_view(const IntraWalk& A) {          // the candidate CU itself, in the picture
+  IwView W;
+  W.n = A.n; W.jobs = A.jobs; W.syn = A.syn; W.csyn = A.csyn; W.opt = A.opt; W.tmp = A.tmp; W.coef_tmp = A.coef_tmp; W.res = A.res;
+  W.pic = A.pic; W.rec_y = A.rec_y; W.rec_cb = A.rec_cb; W.rec_cr = A.rec_cr;
+  return W;
+}
 
-#define IW_LEAF(JOBS, CTX, OFF, LEVELS, RES) turd_fused_body(L.leaf, i, JOBS, A.n, A.pic, CTX, OFF, A.entropy_bits, A.scans, A.lcoef, LEVELS, A.zs, A.ns, A.as, A.fr, A.rq, A.cb, A.lwork, RES, \
-                                                             A.rec_y, A.rec_cb, A.rec_cr)
+#define IW_LEAF(JOBS, CTX, OFF, LEVELS, RES) turd_fused_body(L.leaf, i, JOBS, W.n, W.pic, CTX, OFF, A.entropy_bits, A.scans, A.lcoef, LEVELS, A.zs, A.ns, A.as, A.fr, A.rq, A.cb, A.lwork, RES, \
+                                                             W.rec_y, W.rec_cb, W.rec_cr)
 
 // one pass of xRecurIntraCodingQT over the PU (hop_launch_intra_rqt with the pass's direction in syn): results into A.tmp / A.coef_tmp
-__device__ static void walk_intra_rqt(const IntraWalk& A, WalkShared& L, CabacLds1& sh1, const int i, const int tr_depth0, const int check_first) {
+__device__ static __forceinline__ void walk_intra_rqt(const IntraWalk& A, const IwView& W, WalkShared& L_, CabacLds1& sh1_, const int i, const int tr_depth0, const int check_first) {
+  WalkShared& L = *hopd_lds(&L_); CabacLds1& sh1 = *hopd_lds(&sh1_);   // (the kernels' __shared__ objects, also where this becomes a function of its own)
   const int tid = threadIdx.x;
   const RqtClass k = A.k;
-  const int parts = 1 << (2 * (k.log2_cu - 2)), pitch = A.pic.pic_w;
-  if (tid == 0) irqt_init_body(i, A.jobs, A.ctx_in, A.cu_in, A.cur, A.cucur, A.irwork, A.tmp);
+  const int parts = 1 << (2 * (k.log2_cu - 2)), pitch = W.pic.pic_w;
+  if (tid == 0) irqt_init_body(i, W.jobs, A.ctx_in, A.cu_in, A.cur, A.cucur, A.irwork, W.tmp);
   __syncthreads();
   int s_rel[4], s_child[4];
   int sp = 0;
@@ -269,22 +302,22 @@ __device__ static void walk_intra_rqt(const IntraWalk& A, WalkShared& L, CabacLd
     nd.check_split = log2 > k.log2_min_tu && !(check_first && nd.check_full);
     nd.ts_y = (k.use_ts && nd.check_full && log2 == 2) ? 1 : 0;
     if (s_child[sp] < 0) {
-      if (tid == 0) irqt_begin_body(i, k, nd, A.jobs, A.syn, A.opt, A.bd_y, A.cur, A.cucur, A.root[d], A.curoot[d], A.tmp, A.irwork, A.pj, A.modes, A.tuj, A.off, A.tuj2, A.off2, A.ts_base, nullptr);
+      if (tid == 0) irqt_begin_body(i, k, nd, W.jobs, W.syn, W.opt, A.bd_y, A.cur, A.cucur, A.root[d], A.curoot[d], W.tmp, A.irwork, A.pj, A.modes, A.tuj, A.off, A.tuj2, A.off2, A.ts_base, nullptr);
       __syncthreads();
       if (nd.check_full) {
-        intra_pred_body(L.intra, A.pj + i, A.modes[i], A.pic, A.rec_y);
+        intra_pred_body(L.intra, A.pj + i, A.modes[i], W.pic, W.rec_y);
         __syncthreads();
         if (nd.ts_y) {
           IW_LEAF(A.tuj2, A.root[d], A.off2, A.coef, A.tr2);
           __syncthreads();
-          irqt_copy_body(i, tid, 256, 1, k, nd, A.jobs, A.syn, A.irwork, A.rec_y, pitch, A.recl, A.park, nullptr);
+          irqt_copy_body(i, tid, 256, 1, k, nd, W.jobs, W.syn, A.irwork, W.rec_y, pitch, A.recl, A.park, nullptr);
           __syncthreads();
         }
         IW_LEAF(A.tuj, A.root[d], A.off, A.coef, A.tr);
         __syncthreads();
-        if (nd.check_split) { irqt_copy_body(i, tid, 256, 0, k, nd, A.jobs, A.syn, A.irwork, A.rec_y, pitch, A.recl, A.park, nullptr); __syncthreads(); }
-        if (tid == 0) irqt_single_body(sh1, 0, i, k, nd, A.jobs, A.syn, A.opt, A.cur, A.cucur, A.root[d], A.curoot[d], A.test[d], A.cutest[d], A.tmp, A.irwork, A.tr, A.tr2, A.coef, A.ts_base,
-                                       A.rec_y, pitch, A.park, A.scans, nullptr);
+        if (nd.check_split) { irqt_copy_body(i, tid, 256, 0, k, nd, W.jobs, W.syn, A.irwork, W.rec_y, pitch, A.recl, A.park, nullptr); __syncthreads(); }
+        if (tid == 0) irqt_single_body(sh1, 0, i, k, nd, W.jobs, W.syn, W.opt, A.cur, A.cucur, A.root[d], A.curoot[d], A.test[d], A.cutest[d], W.tmp, A.irwork, A.tr, A.tr2, A.coef, A.ts_base,
+                                       W.rec_y, pitch, A.park, A.scans, nullptr);
         __syncthreads();
       }
       if (!nd.check_split) { sp--; continue; }
@@ -296,18 +329,18 @@ __device__ static void walk_intra_rqt(const IntraWalk& A, WalkShared& L, CabacLd
       sp++;
       continue;
     }
-    if (tid == 0) irqt_close_body(sh1, 0, i, k, nd, A.jobs, A.syn, A.cur, A.cucur, A.root[d], A.curoot[d], A.test[d], A.cutest[d], A.tmp, A.irwork, A.coef, A.scans, nullptr);
+    if (tid == 0) irqt_close_body(sh1, 0, i, k, nd, W.jobs, W.syn, A.cur, A.cucur, A.root[d], A.curoot[d], A.test[d], A.cutest[d], W.tmp, A.irwork, A.coef, A.scans, nullptr);
     __syncthreads();
-    if (nd.check_full) { irqt_copy_body(i, tid, 256, 2, k, nd, A.jobs, A.syn, A.irwork, A.rec_y, pitch, A.recl, A.park, nullptr); __syncthreads(); }
+    if (nd.check_full) { irqt_copy_body(i, tid, 256, 2, k, nd, W.jobs, W.syn, A.irwork, W.rec_y, pitch, A.recl, A.park, nullptr); __syncthreads(); }
     sp--;
   }
-  irqt_final_body(i, tid, 256, k, tr_depth0, A.syn, A.irwork, A.tmp, A.coef, A.coef_tmp, A.cur, A.cucur, nullptr, nullptr, nullptr);
+  irqt_final_body(i, tid, 256, k, tr_depth0, W.syn, A.irwork, W.tmp, A.coef, W.coef_tmp, A.cur, A.cucur, nullptr, nullptr, nullptr);
   __syncthreads();
 }
 
 // ---- the phases of an intra candidate, each on the whole workgroup, index i into the arrays of A ----
 // estIntraPredQT of PU pu up to the candidate list (:2430-2493)
-__device__ static void iw_luma_prep(const IntraWalk& A, WalkShared& L, const int i, const int pu) {
+__device__ static __forceinline__ void iw_luma_prep(const IntraWalk& A, WalkShared& L, const int i, const int pu) {
   if (threadIdx.x == 0) is_prep_body(i, A.k, pu, A.nxn, A.jobs, A.sj, A.opt, A.ctx_in, A.cu_in, A.sres, A.syn, A.rj, A.mj, A.iswork);
   __syncthreads();
   intra_rough_body(L.intra, A.rj + i, A.pic, A.rec_y, A.satd + (size_t)i * 35);
@@ -317,13 +350,13 @@ __device__ static void iw_luma_prep(const IntraWalk& A, WalkShared& L, const int
 }
 // the best mode again with the full tree, the better result kept, the decided PU into the picture (:2555-2660).  Where that pass repeats the winner it is left out, and the
 // commit puts the last PU's block into the picture too, where the pass would have left it (`skip` is uniform over the grid: every barrier is reached by all or by none)
-__device__ static void iw_luma_final(const IntraWalk& A, WalkShared& L, CabacLds1& sh1, const int i, const int pu) {
+__device__ static __forceinline__ void iw_luma_final(const IntraWalk& A, WalkShared& L, CabacLds1& sh1, const int i, const int pu) {
   const int tid = threadIdx.x, n_max = A.num_full_rd + 2, pitch = A.pic.pic_w;
   const bool skip = !A.final_always && rqt_intra_final_repeats(A.k, A.nxn);
   if (tid == 0) is_pick_body(i, pu, n_max, n_max, A.mres, A.iswork, A.syn, A.active);
   __syncthreads();
   if (!skip) {
-    walk_intra_rqt(A, L, sh1, i, A.nxn, 0);
+    walk_intra_rqt(A, iw_view(A), L, sh1, i, A.nxn, 0);
     is_keep_body(i, tid, 256, A.k, pu, A.nxn, n_max, n_max, A.jobs, A.mres, A.syn, A.tmp, A.coef_tmp, A.rec_y, pitch, A.iswork, A.coef_out, A.reco_y);
     __syncthreads();
   }
@@ -331,12 +364,13 @@ __device__ static void iw_luma_final(const IntraWalk& A, WalkShared& L, CabacLds
   __syncthreads();
 }
 // one direction of estIntraPredChromaQT along the luma tree in A.res[i] (xRecurIntraChromaCodingQT :2130-2277), then the CU's chroma bits and cost (ic_bits)
-__device__ static void iw_chroma_mode(const IntraWalk& A, WalkShared& L, CabacLds1& sh1, const int i, const int m) {
+__device__ static __forceinline__ void iw_chroma_mode(const IntraWalk& A, const IwView& W, WalkShared& L_, CabacLds1& sh1_, const int i, const int m) {
+  WalkShared& L = *hopd_lds(&L_); CabacLds1& sh1 = *hopd_lds(&sh1_);
   const int tid = threadIdx.x;
   const RqtClass k = A.k;
-  const int parts = 1 << (2 * (k.log2_cu - 2)), pitch_c = A.pic.pic_w >> 1;
-  const hop_rqt_result* r = A.res + i;
-  if (tid == 0) ic_mode_body(i, m, A.jobs, A.ctx_in, A.ccur, A.csyn, A.icwork);
+  const int parts = 1 << (2 * (k.log2_cu - 2)), pitch_c = W.pic.pic_w >> 1;
+  const hop_rqt_result* r = W.res + i;
+  if (tid == 0) ic_mode_body(i, m, W.jobs, A.ctx_in, A.ccur, W.csyn, A.icwork);
   __syncthreads();
   int s_part[4], s_child[4];
   int sp = 0;
@@ -349,24 +383,24 @@ __device__ static void iw_chroma_mode(const IntraWalk& A, WalkShared& L, CabacLd
       if (tr == d && log2 <= k.log2_max_tu && !(log2 == 2 && (part & 3))) {       // a transform unit of this CU sits here (ic_leaf_here)
         const bool may_ts = k.use_ts && log2 <= 3;
         for (int comp = 1; comp <= 2; comp++) {
-          if (tid == 0) ic_begin_body(i, k, nd, comp, A.jobs, A.csyn, A.opt, A.bd_c, A.ccur, A.croot, A.res, A.icwork, A.pj, A.modes, A.tuj, A.off, A.tuj2, A.off2, A.ts_base);
+          if (tid == 0) ic_begin_body(i, k, nd, comp, W.jobs, W.csyn, W.opt, A.bd_c, A.ccur, A.croot, W.res, A.icwork, A.pj, A.modes, A.tuj, A.off, A.tuj2, A.off2, A.ts_base);
           __syncthreads();
           if (comp == 1) {
-            intra_pred_chroma_body(L.intra, A.pj + i, A.modes[i], 1, A.pic, A.rec_cb, A.rec_cr);
+            intra_pred_chroma_body(L.intra, A.pj + i, A.modes[i], 1, W.pic, W.rec_cb, W.rec_cr);
             __syncthreads();
-            intra_pred_chroma_body(L.intra, A.pj + i, A.modes[i], 2, A.pic, A.rec_cb, A.rec_cr);
+            intra_pred_chroma_body(L.intra, A.pj + i, A.modes[i], 2, W.pic, W.rec_cb, W.rec_cr);
             __syncthreads();
           }
-          int16_t* recc = comp == 1 ? A.rec_cb : A.rec_cr;
+          int16_t* recc = comp == 1 ? W.rec_cb : W.rec_cr;
           if (may_ts) {
             IW_LEAF(A.tuj2, A.ccur, A.off2, A.ccoef, A.tr2);
             __syncthreads();
-            if (tid < 16) ic_park_body(i, tid, k, nd, A.jobs, A.opt, A.res, recc, pitch_c, A.cpark);
+            if (tid < 16) ic_park_body(i, tid, k, nd, W.jobs, W.opt, W.res, recc, pitch_c, A.cpark);
             __syncthreads();
           }
           IW_LEAF(A.tuj, A.ccur, A.off, A.ccoef, A.tr);
           __syncthreads();
-          if (tid == 0) ic_single_body(sh1, 0, i, k, nd, comp, A.jobs, A.csyn, A.opt, A.ccur, A.croot, A.res, A.icwork, A.tr, A.tr2, A.ccoef, A.ts_base, recc, pitch_c, A.cpark, A.scans);
+          if (tid == 0) ic_single_body(sh1, 0, i, k, nd, comp, W.jobs, W.csyn, W.opt, A.ccur, A.croot, W.res, A.icwork, A.tr, A.tr2, A.ccoef, A.ts_base, recc, pitch_c, A.cpark, A.scans);
           __syncthreads();
         }
       }
@@ -379,11 +413,11 @@ __device__ static void iw_chroma_mode(const IntraWalk& A, WalkShared& L, CabacLd
       sp++;
       continue;
     }
-    if (tid == 0) ic_fold_body(i, k, nd, A.res);
+    if (tid == 0) ic_fold_body(i, k, nd, W.res);
     __syncthreads();
     sp--;
   }
-  if (tid == 0) ic_bits_body(sh1, 0, i, k, A.jobs, A.csyn, A.ctx_in, A.cu_in, A.res, A.icwork, A.ccoef, A.scans);
+  if (tid == 0) ic_bits_body(sh1, 0, i, k, W.jobs, W.csyn, A.ctx_in, A.cu_in, W.res, A.icwork, A.ccoef, A.scans);
   __syncthreads();
 }
 __device__ static inline void iw_zero_ccoef(const IntraWalk& A, const int i) {
@@ -395,8 +429,9 @@ __device__ static inline void iw_zero_ccoef(const IntraWalk& A, const int i) {
 // getTotalDistortion, the CU's bits from the CI_CURR_BEST state, calcRdCost
 __device__ static inline void iw_total(const IntraWalk& A, CabacLds1& sh1, const int i) {
   if (threadIdx.x == 0) {
+    const RqtClass k = A.k;                                              // (a copy: a reference into A handed to a function of its own would put the whole table on the stack)
     A.dist[i] = A.sres[i].dist + A.cres[i].dist;
-    intra_cu_total_body(sh1, 0, i, A.k, A.jobs, A.syn_out, A.res, A.coef_out, A.ctx_in, A.cu_in, A.dist, A.bits, A.cost, A.ctx_out, A.cu_out, A.scans);
+    intra_cu_total_body(sh1, 0, i, k, A.jobs, A.syn_out, A.res, A.coef_out, A.ctx_in, A.cu_in, A.dist, A.bits, A.cost, A.ctx_out, A.cu_out, A.scans);
   }
 }
 
@@ -417,7 +452,7 @@ __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_intra_walk(IntraWa
       if (tid == 0) is_pick_body(i, pu, pass, n_max, A.mres, A.iswork, A.syn, A.active);
       __syncthreads();
       if (!A.active[i]) continue;                                        // this CU's list is shorter (uniform over the workgroup)
-      walk_intra_rqt(A, L, sh1, i, A.nxn, 1);
+      walk_intra_rqt(A, iw_view(A), L, sh1, i, A.nxn, 1);
       is_keep_body(i, tid, 256, k, pu, A.nxn, pass, n_max, A.jobs, A.mres, A.syn, A.tmp, A.coef_tmp, A.rec_y, pitch, A.iswork, A.coef_out, A.reco_y);
       __syncthreads();
     }
@@ -427,7 +462,7 @@ __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_intra_walk(IntraWa
   iw_zero_ccoef(A, i);
   __syncthreads();
   for (int m = 0; m < 5; m++) {
-    iw_chroma_mode(A, L, sh1, i, m);
+    iw_chroma_mode(A, iw_view(A), L, sh1, i, m);
     ic_keep_body(i, tid, 256, k, A.jobs, A.res, A.icwork, A.ccoef, A.rec_cb, A.rec_cr, pitch_c, A.coef_out, A.reco_c);
     __syncthreads();
   }
@@ -449,10 +484,11 @@ __device__ static inline void iw_band_prepare(const int16_t* pic, int16_t* band,
     band[(ptrdiff_t)(by + r) * pitch + bx + q] = pic[(ptrdiff_t)(by + r) * pitch + bx + q];
   }
 }
-// A with the arrays and pictures of virtual candidate v of CU i (whose job sits at picture row y0): the bodies called with index v then work on v's copies and band
-__device__ static inline IntraWalk iw_virtual(const IntraWalk& A, const int v, const int y0) {
-  IntraWalk B = A;
+// the arrays and pictures of virtual candidate v of CU i (whose job sits at picture row y0): the bodies called with index v then work on v's copies and band
+__device__ static inline IwView iw_virtual(const IntraWalk& A, const int v, const int y0) {
+  IwView B;
   B.n = A.V; B.jobs = A.vjobs; B.syn = A.vsyn; B.csyn = A.vsyn; B.opt = A.vopt; B.tmp = A.vtmp; B.coef_tmp = A.vcoef_tmp; B.res = A.vres;
+  B.pic = A.pic;
   const ptrdiff_t pitch = A.pic.pic_w, pitch_c = A.pic.pic_w >> 1;
   const ptrdiff_t sy = ((ptrdiff_t)v * A.hb + 1 - y0) * pitch, sc = ((ptrdiff_t)v * A.hbc + 1 - (y0 >> 1)) * pitch_c;
   B.pic.pred_y = A.band_pred[0] + sy; B.pic.pred_cb = A.band_pred[1] + sc; B.pic.pred_cr = A.band_pred[2] + sc;
@@ -480,11 +516,11 @@ __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_iw_cand(IntraWalk 
   const hop_rqt_job jb = A.jobs[i];
   if (tid == 0) { A.vjobs[v] = jb; hop_intra_cu_syntax y = A.syn[i]; y.luma_dir[pu] = (int)A.mres[i].modes[pass]; A.vsyn[v] = y; }
   { const uint32_t* so = (const uint32_t*)(A.opt + i); uint32_t* dq = (uint32_t*)(A.vopt + v); for (int e = tid; e < (int)(sizeof(hop_intra_rqt_opt) / 4); e += 256) dq[e] = so[e]; }
-  const IntraWalk B = iw_virtual(A, v, jb.y);
+  const IwView B = iw_virtual(A, v, jb.y);
   const int cu = 1 << A.k.log2_cu, N = cu >> A.nxn, parts = 1 << (2 * (A.k.log2_cu - 2)), part = pu * (parts >> (2 * A.nxn));
   iw_band_prepare(A.rec_y, B.rec_y, A.pic.pic_w, A.pic.pic_w, A.pic_h, jb.x + rqt_zx(part), jb.y + rqt_zy(part), N);
   __syncthreads();
-  walk_intra_rqt(B, L, sh1, v, A.nxn, 1);
+  walk_intra_rqt(A, B, L, sh1, v, A.nxn, 1);
 }
 
 // the decisions over the candidate passes in their order (strict '<': the first of equal costs stays), the winner's arrays, levels and block kept (xSetIntraResultQT), then
@@ -506,7 +542,7 @@ __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_iw_pick(IntraWalk 
   {
     const int v = i * A.P + s_best;
     const hop_rqt_job jb = A.jobs[i];
-    const IntraWalk B = iw_virtual(A, v, jb.y);
+    const IwView B = iw_virtual(A, v, jb.y);
     const int cu = 1 << k.log2_cu, parts = 1 << (2 * (k.log2_cu - 2)), q = parts >> (2 * A.nxn), part = pu * q, N = cu >> A.nxn, x0 = rqt_zx(part), y0 = rqt_zy(part);
     const size_t cu2 = (size_t)cu * cu, cbi = (size_t)i * (cu2 + (cu2 >> 1)), cbv = (size_t)v * (cu2 + (cu2 >> 1));
     IsWork* w = A.iswork + i; const hop_rqt_result* t = A.vtmp + v;
@@ -533,14 +569,14 @@ __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_iw_chroma(IntraWal
   if (tid == 0) { A.vjobs[v] = jb; A.vsyn[v] = A.syn_out[i]; }
   { const uint32_t* so = (const uint32_t*)(A.opt + i); uint32_t* dq = (uint32_t*)(A.vopt + v); for (int e = tid; e < (int)(sizeof(hop_intra_rqt_opt) / 4); e += 256) dq[e] = so[e]; }
   { const uint32_t* so = (const uint32_t*)(A.res + i); uint32_t* dq = (uint32_t*)(A.vres + v); for (int e = tid; e < (int)(sizeof(hop_rqt_result) / 4); e += 256) dq[e] = so[e]; }
-  const IntraWalk B = iw_virtual(A, v, jb.y);
+  const IwView B = iw_virtual(A, v, jb.y);
   const int cu = 1 << A.k.log2_cu, pw = A.pic.pic_w >> 1;
   iw_band_prepare(A.rec_cb, B.rec_cb, pw, pw, A.pic_h >> 1, jb.x >> 1, jb.y >> 1, cu >> 1);
   iw_band_prepare(A.rec_cr, B.rec_cr, pw, pw, A.pic_h >> 1, jb.x >> 1, jb.y >> 1, cu >> 1);
-  iw_zero_ccoef(B, v);
+  iw_zero_ccoef(A, v);
   if (tid == 0) A.icwork[v].best_cost = 1.7e+308;                           // (a private record per direction: ic_bits_body leaves this direction's cost there)
   __syncthreads();
-  iw_chroma_mode(B, L, sh1, v, m);                                         // (ic_mode_body resets the best cost for m == 0 only: the comparison below reads icwork[v].dist / the cost it forms)
+  iw_chroma_mode(A, B, L, sh1, v, m);                                         // (ic_mode_body resets the best cost for m == 0 only: the comparison below reads icwork[v].dist / the cost it forms)
 }
 
 // the decisions over the five directions in their order, xSetIntraResultChromaQT for the winner, the CU's totals
@@ -557,7 +593,7 @@ __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_iw_finish(IntraWal
   __syncthreads();
   const int v = i * A.P + s_best;
   const hop_rqt_job jb = A.jobs[i];
-  const IntraWalk B = iw_virtual(A, v, jb.y);
+  const IwView B = iw_virtual(A, v, jb.y);
   const int cu = 1 << k.log2_cu, half = cu >> 1, parts = 1 << (2 * (k.log2_cu - 2)), pitch_c = A.pic.pic_w >> 1;
   const size_t cu2 = (size_t)cu * cu, h2 = cu2 >> 2;
   const hop_rqt_result* r = A.vres + v;
@@ -654,6 +690,7 @@ int hop_launch_intra_walk(hop_ctx* c, const hop_intra_class& q, const hop_cabac_
     A.band_rec[0] = (int16_t*)take(by); A.band_rec[1] = (int16_t*)take(bc); A.band_rec[2] = (int16_t*)take(bc);
   }
   if (o > buf_bytes) return hop_set_err(c, HOP_ERR_STATE, "intra walk: work buffer too small (%zu > %zu)", o, buf_bytes);
+  { const int r = walk_fill(c, vbuf, buf_bytes); if (r) return r; }
   A.entropy_bits = hop_entropy_bits_device(c); A.scans = c->rdoq_scans; A.rec_y = c->rec[0]; A.rec_cb = c->rec[1]; A.rec_cr = c->rec[2];
   const int pr = hop_prof_begin(c, A.nxn ? HOP_K_WALK_INTRA_NXN : HOP_K_WALK_INTRA + (k.log2_cu - 3), (uint64_t)n);
   if (!par) hipLaunchKernelGGL(k_intra_walk, dim3(n), dim3(256), 0, c->stream, A);
