@@ -13,6 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libhophip.so")
 
 HOP_STAGE_INT, HOP_STAGE_FRAC, HOP_STAGE_GT = 1, 2, 3
+HOP_ERR_ARG = -1
 HOP_FLAG_FEN, HOP_FLAG_HADME = 1, 2
 HOP_TU_RD_TS, HOP_TU_RD_KEEP = 1, 2
 HOP_DIST_SAD, HOP_DIST_SSE, HOP_DIST_HADS = 0, 1, 2
@@ -265,7 +266,9 @@ class Context:
 
     def _chk(self, r, what):
         if r != 0:
-            raise HopError("%s: %d %s" % (what, r, self.L.hop_last_error(self.h).decode()))
+            e = HopError("%s: %d %s" % (what, r, self.L.hop_last_error(self.h).decode()))
+            e.code = r                  # HOP_ERR_*
+            raise e
 
     def upload_orig(self, Y, Cb, Cr):
         Y, Cb, Cr = (np.ascontiguousarray(a, np.int16) for a in (Y, Cb, Cr))
@@ -594,6 +597,41 @@ class Context:
 
     def sync(self):
         self._chk(self.L.hop_sync(self.h), "hop_sync")
+
+    # ---- the spine's byte-moving entries (csrc/k_spine.hip), as hop_encode_frame's backend calls them ----
+    def valid_pattern(self, queries):
+        """hop_valid_pattern: queries (n, 6) int32 -- x, y, w, h, mv_x, mv_y (quarter samples) -> (n,) uint8, 1 where both probes of isValidPattern hit committed samples"""
+        q = np.ascontiguousarray(queries, np.int32).reshape(-1, 6)
+        out = np.zeros(len(q), np.uint8)
+        self.L.hop_valid_pattern.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+        self._chk(self.L.hop_valid_pattern(self.h, len(q), q.ctypes.data, out.ctypes.data), "hop_valid_pattern")
+        return out
+
+    def recon_stash(self, rects, restore=False):
+        """hop_recon_stash: rects (n, 4) int32 -- x, y (+ k * pic_h: copy k of the candidate slots), size, stash slot; the blocks of the reconstruction picture (and of
+        the levels, once hop_encode_frame has run) put aside, or with restore brought back"""
+        r = np.ascontiguousarray(rects, np.int32).reshape(-1, 4)
+        self.L.hop_recon_stash.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
+        self._chk(self.L.hop_recon_stash(self.h, len(r), r.ctypes.data, 1 if restore else 0), "hop_recon_stash")
+
+    def ssref_commit_recon(self, rects):
+        """hop_ssref_commit_recon: rects (n, 3) -- x, y, size: the blocks of the resident reconstruction picture committed to the SS reference"""
+        r4 = np.zeros((len(rects), 4), np.int32)
+        r4[:, :3] = np.asarray(rects, np.int32).reshape(-1, 3)
+        self.L.hop_ssref_commit_recon.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        self._chk(self.L.hop_ssref_commit_recon(self.h, len(r4), r4.ctypes.data), "hop_ssref_commit_recon")
+
+    def recon_put_device(self, n, d_jobs, d_reco_y, d_reco_c):
+        """hop_recon_put_device: n CUs of ONE size (RQT_JOB_DTYPE: x, y, log2_cu) from packed planes into the reconstruction picture; the arguments are device
+        addresses, the copy is enqueued on the context's stream"""
+        self.L.hop_recon_put_device.argtypes = [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 3
+        self._chk(self.L.hop_recon_put_device(self.h, n, d_jobs, d_reco_y, d_reco_c), "hop_recon_put_device")
+
+    def coef_put_device(self, n, d_jobs, d_coef):
+        """hop_coef_put_device: the levels of the same CUs (1.5 size^2 per CU; d_coef None: CUs without residual) into the image of the levels, which exists once
+        hop_encode_frame has run on the context"""
+        self.L.hop_coef_put_device.argtypes = [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 2
+        self._chk(self.L.hop_coef_put_device(self.h, n, d_jobs, d_coef), "hop_coef_put_device")
 
 
 def decode_schedule(W, H, parts, schedule=0, lib=None):

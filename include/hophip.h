@@ -629,7 +629,8 @@ int hop_sizeof(const char* name);
  * the caller clipped it): out[i] = 1 if the two probe samples below the displaced block are not the sentinel. */
 int hop_valid_pattern(hop_ctx* ctx, int n, const int32_t* xywh_mv, uint8_t* out);
 /* replaces: the bookkeeping of m_ppcRecoYuvBest / Temp in TEncCu::xCheckBestMode (TLibEncoder/TEncCu.cpp:1572-1575) and xCopyYuv2Pic (:1623-1662): n blocks
- * rect4 = {x, y, size, slot} of the reconstruction picture put aside into stash slots (restore = 0) or brought back (restore = 1); 1024 slots. */
+ * rect4 = {x, y, size, slot} of the reconstruction picture put aside into stash slots (restore = 0) or brought back (restore = 1); y may name a copy of the
+ * candidate slots (y + k * pic_h, hop_ctx_set_slots); slots 0 .. 32767 (16 per CTU row in flight).  Once hop_encode_frame has run on the context the blocks' levels travel with them. */
 int hop_recon_stash(hop_ctx* ctx, int n, const int32_t* rect4, int restore);
 /* replaces: TComYuv::copyToPicYuv of an intra candidate's reconstruction (TEncCu.cpp:1476, :1640): the packed blocks hop_intra_cu_device_classes leaves in d_reco_y /
  * d_reco_c into the reconstruction picture at the jobs' positions; asynchronous on the context stream. */

@@ -451,3 +451,104 @@ def test_ctu_rows_sharded_cancel_is_agreed_between_the_ranks():
     done = cost > 0
     assert 2 <= int(done.sum()) < len(cost) and int(done.sum()) == int(retired.sum())
     assert np.array_equal(cost[done], G[key + "/cost"][done])
+
+
+# ---- partial CTUs on the right AND below inside a wavefront: 432x184 (6 CTU columns + one 48 wide, 2 CTU rows + one 56 tall: the remainders of bench.py's 7728x5368 frame;
+# 21 CTUs, seven columns being the narrowest at which a lag-5 wavefront is not raster order).  Goldens from the reference encoder run with WaveFrontSynchro and one substream
+# per CTU row, with its reconstruction before the loop filters: oracle/make_golden26.py -> tests/golden/encoder_spine_ragged.npz ----
+RAGGED_W, RAGGED_H, RAGGED_SEED = 432, 184, 3
+RAGGED = [("432x184_seed3_wpp", 16), ("432x184_seed3_mi15_wpp", 15)]      # key, lenslet pitch = MIsize
+_ragged = {}
+
+
+def ragged_golden():
+    if "G" not in _ragged:
+        with np.load(os.path.join(ROOT, "tests", "golden", "encoder_spine_ragged.npz")) as z:
+            _ragged["G"] = {k: z[k] for k in z.files}
+    return _ragged["G"]
+
+
+def ragged_picture(mi=16, seed=RAGGED_SEED):
+    return lenslet(RAGGED_W, RAGGED_H, mi, seed)
+
+
+def check_recon_against_golden(G, key, rec):
+    """rec: the three planes before the loop filters, against the reference encoder's"""
+    for c, name in enumerate(("rec_y", "rec_cb", "rec_cr")):
+        want = G[key + "/" + name]
+        assert want.shape == np.asarray(rec[c]).shape, (key, name)
+        assert np.array_equal(rec[c], want), (key, name, np.argwhere(np.asarray(rec[c]) != want)[:5])
+
+
+def check_parts_against_golden(G, key, parts):
+    """the finished per-partition data of every CTU (check_against_golden without the candidate trace and the per-CTU totals)"""
+    R = G[key + "/parts"]
+    assert R.shape[0] == len(parts)
+    for a in range(R.shape[0]):
+        r, q = R[a], parts[a]
+        used = r[:, 1] != 15
+        for name, col in (("depth", 0), ("pred_mode", 1), ("part_size", 2), ("skip", 3), ("merge_flag", 4), ("merge_idx", 5), ("gt_flag", 6), ("tr_idx", 9)):
+            assert np.array_equal(np.asarray(q[name])[used].astype(np.int16), r[used, col]), (key, a, name)
+        intra, inter = used & (r[:, 1] == 1), used & (r[:, 1] == 0)
+        assert np.array_equal(np.asarray(q["luma_dir"])[intra].astype(np.int16), r[intra, 7]) and np.array_equal(np.asarray(q["chroma_dir"])[intra].astype(np.int16), r[intra, 8]), (key, a)
+        assert np.array_equal(np.asarray(q["cbf"])[used].astype(np.int16), r[used, 10:13]), (key, a)
+        assert np.array_equal(np.asarray(q["mv"])[inter], r[inter, 13:15]) and np.array_equal(np.asarray(q["gt"])[inter], r[inter, 15:23]), (key, a)
+
+
+@pytest.mark.parametrize("lag", [0, 5])
+@pytest.mark.parametrize("key,mi", RAGGED)
+def test_spine_wavefront_with_partial_ctus_equals_the_reference(key, mi, lag, monkeypatch):
+    """the bottom CTU row of a wavefront 56 rows tall, its last column 48 wide: every candidate, the per-CTU totals, the partition data AND the reconstruction of the
+    reference encoder, the CTUs one after the other (lag 0) and as a lag-5 wavefront with candidate slots (MIsize 15 with 48 of them, as bench.py codes its frame)"""
+    G = ragged_golden()
+    L = spine_cpu()
+    if mi == 15: monkeypatch.setenv("HOP_SPEC_SLOTS", "48")
+    elif lag: monkeypatch.setenv("HOP_SPEC_SLOTS", "16")
+    Y, Cb, Cr = ragged_picture(mi)
+    cost, bits, dist, parts, rec, text, rr = run_cpu_wpp(L, RAGGED_W, RAGGED_H, Y, Cb, Cr, lag, mi=mi)
+    check_against_golden(G, key, cost, bits, dist, parts, text)
+    check_recon_against_golden(G, key, rec)
+    if lag: assert rr[1] > rr[0]
+
+
+@pytest.mark.parametrize("world,take", [(2, 0), (2, 1), (3, 0)])
+def test_ctu_rows_with_partial_ctus_sharded_over_ranks_equal_the_reference(world, take, monkeypatch):
+    """432x184 over two and three ranks: the blocks that cross between the ranks include 48-wide CTUs and the 56-tall bottom row.  Rank `take` must end with the whole
+    picture: costs and partition data of the golden, the reference encoder's reconstruction, and every rank retires exactly its rows"""
+    L = spine_cpu()
+    monkeypatch.setenv("HOP_SPEC_SLOTS", "48")
+    G = ragged_golden()
+    key = RAGGED[0][0]
+    W, H = RAGGED_W, RAGGED_H
+    Y, Cb, Cr = ragged_picture()
+    cost, bits, dist, parts, rec, retired = run_cpu_sharded(L, W, H, Y, Cb, Cr, 5, world, take)
+    assert np.array_equal(cost, G[key + "/cost"]) and np.array_equal(bits, G[key + "/bits"]) and np.array_equal(dist, G[key + "/dist"])
+    check_parts_against_golden(G, key, parts)
+    check_recon_against_golden(G, key, rec)
+    rows, cols = (H + 63) // 64, (W + 63) // 64
+    assert list(retired) == [cols * len(range(g, rows, world)) for g in range(world)] == ([14, 7] if world == 2 else [7, 7, 7])
+
+
+def test_stacked_pictures_with_partial_ctus_equal_the_pictures_alone(monkeypatch):
+    """two 240x120 pictures (3 CTU columns + one 48 wide, 1 CTU row + one 56 tall) side by side on one rendezvous: each equals the picture coded alone"""
+    L = spine_cpu()
+    monkeypatch.setenv("HOP_SPEC_SLOTS", "24")
+    W, H, lag, pitch = 240, 120, 5, 448
+    pics = [frame(W, H, 7, False), frame(W, H, 8, False)]
+    cost, bits, dist, parts, rec, rr = run_cpu_stack(L, W, H, pics, pitch, lag)
+    for k, (Y, Cb, Cr) in enumerate(pics):
+        c1, b1, d1, p1, r1, text, _ = run_cpu_wpp(L, W, H, Y, Cb, Cr, lag)
+        assert np.array_equal(cost[k], c1) and np.array_equal(bits[k], b1) and np.array_equal(dist[k], d1), k
+        assert parts[k].tobytes() == p1.tobytes() and np.array_equal(rec[k], r1[0]), k
+    assert rr[1] / rr[0] > 1.5                    # requests of both pictures met in the batches (measured: 1.86)
+
+
+def test_spine_wavefront_direct_with_partial_ctus_equals_the_reference():
+    """Encoder::encode_frame_wavefront_direct (what hop_encode_frame runs with streams > 1) on 432x184: three CTU rows on three backends, lag 5"""
+    G = ragged_golden()
+    L = spine_cpu()
+    key = RAGGED[0][0]
+    Y, Cb, Cr = ragged_picture()
+    cost, bits, dist, parts, rec, text, rr = run_cpu_wpp(L, RAGGED_W, RAGGED_H, Y, Cb, Cr, 5, n_lanes=3)
+    check_against_golden(G, key, cost, bits, dist, parts, text)
+    check_recon_against_golden(G, key, rec)

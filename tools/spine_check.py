@@ -8,7 +8,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from hoputil import lenslet, sharp_frame
 
-def run_reference(W, H, seed, sharp, td, qp=32, mi=16, wpp=False, pitch=16):
+def run_reference(W, H, seed, sharp, td, qp=32, mi=16, wpp=False, pitch=16, extra=()):
+    """extra: further command-line options of the encoder, after the others"""
     Y, Cb, Cr = sharp_frame(W, H, seed) if sharp else lenslet(W, H, pitch, seed)
     with open(os.path.join(td, "in.yuv"), "wb") as f:
         f.write(Y.astype(np.uint8).tobytes() + Cb.astype(np.uint8).tobytes() + Cr.astype(np.uint8).tobytes())
@@ -16,7 +17,7 @@ def run_reference(W, H, seed, sharp, td, qp=32, mi=16, wpp=False, pitch=16):
     t0 = time.time()
     r = subprocess.run([os.path.join(ROOT, "oracle", "_ref", "TAppEncoderShim"), "-c", "/root/reference/cfg/3DHencoder_intra_main.cfg", "-i", "in.yuv", "-wdt", str(W), "-hgt", str(H),
                         "-fr", "30", "-f", "1", "-q", str(qp), "--MIsize=%d" % mi, "-b", "s.bin", "-o", "rec.yuv"] +
-                       (["--WaveFrontSynchro=1", "--WaveFrontSubstreams=%d" % ((H + 63) // 64)] if wpp else []), cwd=td, capture_output=True, text=True, env=env)
+                       (["--WaveFrontSynchro=1", "--WaveFrontSubstreams=%d" % ((H + 63) // 64)] if wpp else []) + list(extra), cwd=td, capture_output=True, text=True, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     return Y, Cb, Cr, time.time() - t0
 
