@@ -61,6 +61,7 @@ struct hop_ctx : hop_lane {
   struct hop_prof_rec* prof_recs; int prof_n, prof_cap;
   double   prof_ms[HOP_K_COUNT];
   uint64_t prof_launches[HOP_K_COUNT], prof_units[HOP_K_COUNT];
+  bool   levels_valid;               // coefpic holds the levels of the picture(s) the context holds: set by a hop_encode_frame that returned HOP_OK, cleared when one starts and by hop_decode_frame
 };
 struct hop_prof_rec { hipEvent_t a, b; int kernel; uint64_t units; };
 int  hop_prof_begin(hop_ctx* c, int kernel, uint64_t units);   // returns record index or -1 when profiling is off

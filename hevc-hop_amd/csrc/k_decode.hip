@@ -224,6 +224,7 @@ extern "C" int hop_decode_frame(hop_ctx* c, const hop_dec_params* p, const hop_c
   const int off_y = 6 * (c->bd_y - 8), off_c = 6 * (c->bd_c - 8);
   if (p->qp < -off_y || p->qp > 51 || p->cb_qp_offset < -12 || p->cb_qp_offset > 12 || p->cr_qp_offset < -12 || p->cr_qp_offset > 12)
     return hop_set_err(c, HOP_ERR_ARG, "hop_decode_frame: qp %d / offsets %d %d out of range", p->qp, p->cb_qp_offset, p->cr_qp_offset);
+  c->levels_valid = false;                                              // the picture is no longer the one hop_encode_frame's resident levels belong to
   const int wctu = (c->pic_w + 63) / 64, hctu = (c->pic_h + 63) / 64, n = wctu * hctu;
   std::vector<int32_t> level(n);
   int32_t n_levels = 0;

@@ -54,48 +54,7 @@ __global__ __launch_bounds__(256) void k_rdoq_classify(const hop_rdoq_job* __res
   }
 }
 
-// ---- scan tables (host), TComRom.cpp:355-481: 3 scans x sides 4..32 + the coefficient-group scans the RDOQ walks ----
-static void rq_diag(uint16_t* T, int w) {                                 // up-right diagonal scan of a w x w grid
-  int next = 0;
-  for (int line = 0; next < w * w; line++) {
-    int prim = line, scnd = 0;
-    while (prim >= w) { scnd++; prim--; }
-    while (prim >= 0 && scnd < w) { T[next++] = (uint16_t)(prim * w + scnd); scnd++; prim--; }
-  }
-}
-void hop_rdoq_build_scans(uint16_t* tabs /* 4080 + 255 entries */) {
-  uint16_t d2[4], d4[16], d8[64];
-  rq_diag(d2, 2); rq_diag(d4, 4); rq_diag(d8, 8);
-  const int offs[4] = { 0, 16, 80, 336 }, cgo[4] = { 0, 1, 5, 21 };
-  for (int l = 2; l <= 5; l++) {
-    const int w = 1 << l, ns = w >> 2;
-    uint16_t* D = tabs + 0 * 1360 + offs[l - 2]; uint16_t* Hs = tabs + 1 * 1360 + offs[l - 2]; uint16_t* V = tabs + 2 * 1360 + offs[l - 2];
-    const uint16_t* cgd = (ns == 1) ? nullptr : (ns == 2) ? d2 : (ns == 4) ? d4 : d8;   // diagonal scan of the group grid
-    if (l == 2) rq_diag(D, 4);
-    else
-      for (int blk = 0; blk < ns * ns; blk++) {
-        const int init = cgd[blk], oy = init / ns, ox = init - oy * ns, offD = 4 * (ox + oy * w);
-        for (int k = 0; k < 16; k++) D[16 * blk + k] = (uint16_t)((d4[k] >> 2) * w + (d4[k] & 3) + offD);
-      }
-    int cnt = 0;
-    for (int by = 0; by < ns; by++) for (int bx = 0; bx < ns; bx++)
-      for (int y = 0; y < 4; y++) for (int x = 0; x < 4; x++) Hs[cnt++] = (uint16_t)((by * 4 + y) * w + bx * 4 + x);
-    cnt = 0;
-    for (int bx = 0; bx < ns; bx++) for (int by = 0; by < ns; by++)
-      for (int x = 0; x < 4; x++) for (int y = 0; y < 4; y++) V[cnt++] = (uint16_t)((by * 4 + y) * w + bx * 4 + x);
-    // group scans: 4x4 -> {0}; 8x8 -> g_sigLastScan8x8[scan]; 16x16 -> the 4x4 scans; 32x32 -> the 8x8 diagonal for every scan
-    for (int s = 0; s < 3; s++) {
-      uint16_t* C = tabs + 4080 + s * 85 + cgo[l - 2];
-      if (l == 2) C[0] = 0;
-      else if (l == 3) { const uint16_t t8[3][4] = { {0, 2, 1, 3}, {0, 1, 2, 3}, {0, 2, 1, 3} }; for (int k = 0; k < 4; k++) C[k] = t8[s][k]; }
-      else if (l == 4) {
-        if (s == 0) for (int k = 0; k < 16; k++) C[k] = d4[k];
-        else if (s == 1) for (int k = 0; k < 16; k++) C[k] = (uint16_t)k;
-        else for (int k = 0; k < 16; k++) C[k] = (uint16_t)((k & 3) * 4 + (k >> 2));
-      } else for (int k = 0; k < 64; k++) C[k] = d8[k];
-    }
-  }
-}
+// (the scan tables are built on the host: hop_rdoq_build_scans, host/hop_hostlogic.cpp)
 
 static const int rq_grid_cap[4] = { 8192, 4096, 2048, 1024 };             // blocks per size class: bounds the work area (about 5 GB at the caps)
 static int rq_blocks(int n, int cls) { const int b = (n + 63) / 64; return b < rq_grid_cap[cls] ? b : rq_grid_cap[cls]; }

@@ -494,7 +494,7 @@ int hop_encode_frame(hop_ctx* c, const hop_enc_params* p, double* ctu_cost, uint
   hopspine::EncConfig cfg;
   if (p->plain_intra) hopspine::default_plain_config(cfg, c->pic_w, pic_h, p->qp, c->bd_y); else hopspine::default_hop_config(cfg, c->pic_w, pic_h, p->qp, p->mi_size);
   cfg.wpp = (p->wpp || p->wavefront_lag > 0) ? 1 : 0;
-  c->enc_progress.store(0); c->enc_cancel.store(0);
+  c->enc_progress.store(0); c->enc_cancel.store(0); c->levels_valid = false;
   cfg.progress = &c->enc_progress; cfg.cancel = &c->enc_cancel;
   if (c->slots > 0 && !p->plain_intra) { cfg.spec_slots = c->slots; cfg.slot_pitch = c->pic_h; }   // hop_ctx_set_slots: the SS/GT candidates of a CU side by side
   struct FnComm : hopspine::ShardComm { hop_ctx* c; void allgather(const void* s, void* r, size_t b) { if (c->shard_fn(c->shard_user, s, r, b) != 0) { hop_set_err(c, HOP_ERR_STATE, "hop_encode_frame: the all-gather callback failed"); throw Bail{ HOP_ERR_STATE }; } } } comm;
@@ -614,6 +614,7 @@ int hop_encode_frame(hop_ctx* c, const hop_enc_params* p, double* ctu_cost, uint
     }
   }
   for (auto e : encs) delete e;
+  c->levels_valid = rc == HOP_OK;
   return rc;
 }
 

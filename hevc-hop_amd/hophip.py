@@ -122,6 +122,14 @@ class DecParams(ctypes.Structure):       # hop_dec_params
     _fields_ = [("qp", ctypes.c_int32), ("cb_qp_offset", ctypes.c_int32), ("cr_qp_offset", ctypes.c_int32), ("plain_intra", ctypes.c_int32), ("schedule", ctypes.c_int32)]
 
 
+HOP_K_ENTROPY_CTX, HOP_K_ENTROPY = 21, 22          # hop_profile_read ids of hop_slice_data_write's context pass and coding pass
+
+
+class SliceDataParams(ctypes.Structure):   # hop_slice_data_params
+    _fields_ = [("qp", ctypes.c_int32), ("slice_type", ctypes.c_int32), ("wpp", ctypes.c_int32), ("plain_intra", ctypes.c_int32), ("sao_luma", ctypes.c_int32),
+                ("sao_chroma", ctypes.c_int32), ("mi_size", ctypes.c_int32)]
+
+
 _I16P = ctypes.POINTER(ctypes.c_int16)
 
 
@@ -135,7 +143,8 @@ MIRRORS = {"hop_pu_job": PU_JOB_DTYPE, "hop_pu_result": PU_RESULT_DTYPE, "hop_pr
            "hop_tu_rd_result": TU_RD_RESULT_DTYPE, "hop_intra_modes_job": INTRA_MODES_JOB_DTYPE, "hop_intra_modes_result": INTRA_MODES_RESULT_DTYPE, "hop_rqt_job": RQT_JOB_DTYPE,
            "hop_rqt_result": RQT_RESULT_DTYPE, "hop_cu_syntax": CU_SYNTAX_DTYPE, "hop_intra_cu_syntax": INTRA_CU_SYNTAX_DTYPE, "hop_intra_rqt_opt": INTRA_RQT_OPT_DTYPE,
            "hop_intra_search_job": INTRA_SEARCH_JOB_DTYPE, "hop_intra_search_result": INTRA_SEARCH_RESULT_DTYPE, "hop_cu_part": CU_PART_DTYPE, "hop_enc_params": EncParams,
-           "hop_deblock_params": DeblockParams, "hop_sao_param": SAO_PARAM_DTYPE, "hop_sao_params": SaoParams, "hop_dec_params": DecParams}
+           "hop_deblock_params": DeblockParams, "hop_sao_param": SAO_PARAM_DTYPE, "hop_sao_params": SaoParams, "hop_dec_params": DecParams,
+           "hop_slice_data_params": SliceDataParams}
 
 
 def mirror_size(m):
@@ -415,6 +424,45 @@ class Context:
         self.L.hop_decode_frame.argtypes = [ctypes.c_void_p] * 4
         self._chk(self.L.hop_decode_frame(self.h, ctypes.byref(p), parts.ctypes.data, levels.ctypes.data), "hop_decode_frame")
 
+    def slice_data_write(self, parts, levels=None, sao_coded=None, qp=32, slice_type=3, wpp=0, plain_intra=0, sao_luma=None, sao_chroma=None, mi_size=16, capacity=None, guard=0):
+        """hop_slice_data_write: the slice data of the context's picture(s) -- parts as encode_frame returned them, levels (n_ctu, 6144) int32 or None = the levels resident
+        after encode_frame, sao_coded (n_ctu, 3) as sao_frame returned them or None (no SAO syntax; the flags default to whether it is given).  Returns (the substreams back to
+        back as bytes, their sizes: uint32, n_substreams per picture each).  capacity: size of the output buffer (default: ample); guard: bytes behind it that must come back
+        untouched (asserted).  An output that does not fit raises HopError with .needed = the bytes it takes."""
+        parts = np.ascontiguousarray(parts, CU_PART_DTYPE)
+        n = self._n_ctu()
+        assert parts.size == n * 256
+        if levels is not None:
+            levels = np.ascontiguousarray(levels, np.int32); assert levels.size == n * 6144
+        if sao_coded is not None:
+            sao_coded = np.ascontiguousarray(sao_coded, SAO_PARAM_DTYPE); assert sao_coded.size == n * 3
+        on = 0 if sao_coded is None else 1
+        p = SliceDataParams(qp, slice_type, wpp, plain_intra, on if sao_luma is None else sao_luma, on if sao_chroma is None else sao_chroma, mi_size)
+        cap = n * 16384 if capacity is None else capacity
+        buf = np.full(cap + guard, 0xA5, np.uint8)
+        sizes = np.zeros(self.pictures * ((self.sub_h + 63) // 64), np.uint32)
+        nsub = ctypes.c_int32(0)
+        self.L.hop_slice_data_write.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_size_t] + [ctypes.c_void_p] * 2
+        r = self.L.hop_slice_data_write(self.h, ctypes.byref(p), parts.ctypes.data, None if levels is None else levels.ctypes.data, None if sao_coded is None else sao_coded.ctypes.data,
+                                        buf.ctypes.data, cap, sizes.ctypes.data, ctypes.byref(nsub))
+        assert np.all(buf[cap:] == 0xA5), "hop_slice_data_write stored past out_capacity"
+        if r != 0:
+            e = HopError("hop_slice_data_write: %d %s" % (r, self.L.hop_last_error(self.h).decode()))
+            e.code = r; e.needed = nsub.value
+            raise e
+        sizes = sizes[:self.pictures * nsub.value]
+        return buf[:int(sizes.sum())].tobytes(), sizes, nsub.value
+
+    def profile(self, on=None, reset=False, read=None):
+        """hop_profile_enable / hop_profile_reset / hop_profile_read: on: switch the HIP events around the launches on or off; reset: clear the sums; read: a HOP_K_* id ->
+        (launches, total ms, units) since the last reset"""
+        if on is not None: self._chk(self.L.hop_profile_enable(self.h, 1 if on else 0), "hop_profile_enable")
+        if reset: self._chk(self.L.hop_profile_reset(self.h), "hop_profile_reset")
+        if read is None: return None
+        la, ms, un = ctypes.c_uint64(0), ctypes.c_double(0), ctypes.c_uint64(0)
+        self._chk(self.L.hop_profile_read(self.h, read, ctypes.byref(la), ctypes.byref(ms), ctypes.byref(un)), "hop_profile_read")
+        return int(la.value), float(ms.value), int(un.value)
+
     def sao_reconstruct_params(self, coded, bit_depth=None):
         """hop_sao_reconstruct_params for this context's picture: coded (n_ctu, 3) SAO_PARAM_DTYPE -> what sao_apply takes"""
         return sao_reconstruct_params(coded, (self.W + 63) // 64, bit_depth or self.bit_depth)
@@ -647,6 +695,31 @@ def decode_schedule(W, H, parts, schedule=0, lib=None):
     if r != 0:
         raise HopError("hop_decode_schedule: %d" % r)
     return lv, int(nl.value)
+
+
+def slice_data_write_host(W, H, parts, levels, sao_coded=None, bit_depth=8, qp=32, slice_type=3, wpp=0, plain_intra=0, sao_luma=None, sao_chroma=None, mi_size=16,
+                          capacity=None, lib=None):
+    """hop_slice_data_write_host: the host build of the slice-data writer (the yardstick of Context.slice_data_write), one picture, no device.  Returns (bytes, sizes, n_substreams);
+    HopError (.code, .needed) as the device entry."""
+    L = lib or load()
+    n = ((W + 63) // 64) * ((H + 63) // 64)
+    parts = np.ascontiguousarray(parts, CU_PART_DTYPE); levels = np.ascontiguousarray(levels, np.int32)
+    assert parts.size == n * 256 and levels.size == n * 6144
+    if sao_coded is not None:
+        sao_coded = np.ascontiguousarray(sao_coded, SAO_PARAM_DTYPE); assert sao_coded.size == n * 3
+    on = 0 if sao_coded is None else 1
+    p = SliceDataParams(qp, slice_type, wpp, plain_intra, on if sao_luma is None else sao_luma, on if sao_chroma is None else sao_chroma, mi_size)
+    cap = n * 16384 if capacity is None else capacity
+    buf = np.zeros(cap, np.uint8); sizes = np.zeros((H + 63) // 64, np.uint32); nsub = ctypes.c_int32(0)
+    L.hop_slice_data_write_host.argtypes = [ctypes.c_int] * 3 + [ctypes.c_void_p] * 5 + [ctypes.c_size_t] + [ctypes.c_void_p] * 2
+    r = L.hop_slice_data_write_host(W, H, bit_depth, ctypes.byref(p), parts.ctypes.data, levels.ctypes.data, None if sao_coded is None else sao_coded.ctypes.data, buf.ctypes.data, cap,
+                                    sizes.ctypes.data, ctypes.byref(nsub))
+    if r != 0:
+        e = HopError("hop_slice_data_write_host: %d" % r)
+        e.code = r; e.needed = nsub.value
+        raise e
+    sizes = sizes[:nsub.value]
+    return buf[:int(sizes.sum())].tobytes(), sizes, nsub.value
 
 
 def decode_footprint(W, H, job, lib=None):

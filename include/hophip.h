@@ -767,6 +767,48 @@ int hop_decode_footprint(int pic_w, int pic_h, const hop_pred_job* pu, int32_t* 
  * candidate or a mode / type out of range. */
 int hop_sao_reconstruct_params(int n_ctu, int ctus_per_row, int bit_depth, const hop_sao_param* coded, hop_sao_param* recon);
 
+/* ---- the entropy coder: a picture's slice data written on the device ---- */
+/* replaces: TEncSlice::encodeSlice (TLibEncoder/TEncSlice.cpp:1228-1500) with TEncCu::encodeCU / xEncodeCU / finishCU (TEncCu.cpp:267-280, :1019-1130, :900-950),
+ * TEncEntropy::encodePredInfo / encodePUWise / encodeCoeff / xEncodeTransform (TEncEntropy.cpp:219-660), the TEncSbac coders (TEncSbac.cpp: codeSplitFlag :731,
+ * codeSkipFlag :599, codePredMode :568, codePartSize :469, codeMergeFlag / Index :630 / :679, codeGTFlag :654, codeMvd :944, codeGT :1051, codeMVPIdx :434,
+ * codeIntraDirLumaAng :770, codeIntraDirChroma :841, codeQtRootCbf :1723, codeQtCbf :1596, codeTransformSubdivFlag :756, codeCoeffNxN :1829-2092, codeSAOBlkParam :2445
+ * with :2097-2170, :2369-2443) and the arithmetic coder TEncBinCABAC (TEncBinCoderCABAC.cpp:78-126, :184-345: encodeBin, encodeBinEP, encodeBinsEP, encodeBinTrm, finish,
+ * writeOut with its buffered byte and 0xFF-run carry), for the picture(s) of the context: the slice data of one slice per picture, in the configurations of
+ * hop_encode_frame (CTU 64, CUs down to 8, transforms 32..4 at three depths, AMP, sign data hiding, transform skip, five merge candidates, no delta QP / PCM / bypass).
+ * parts: 256 hop_cu_part per CTU as hop_encode_frame returned them; levels: host, 6144 per CTU in hop_levels_download's layout, or NULL (below);
+ * sao_coded: 3 per CTU as hop_sao_frame returned them, NULL iff both SAO flags are 0.
+ * levels == NULL means the levels RESIDENT IN THE CONTEXT AFTER hop_encode_frame -- nothing is downloaded or uploaded then.  Only hop_encode_frame leaves levels resident:
+ * hop_decode_frame works from the levels its caller hands it and keeps none, so after it (and after a hop_encode_frame that failed, or before any) a NULL call is
+ * refused with HOP_ERR_STATE instead of coding another picture's levels; the caller of hop_decode_frame passes the levels it already holds.
+ * out receives the substreams back to back, in order; each is RBSP bytes BEFORE emulation prevention and complete: the terminating bin 1, TEncBinCABAC::finish, then the
+ * byte alignment of slice_data (TEncGOP.cpp:1653-1662).  substream_bytes[i] is the length of substream i, *n_substreams their number per picture (wpp: the CTU rows; else
+ * 1); a stacked context writes its pictures one after the other, n_substreams sizes each.  Not written here: VPS / SPS / PPS, the slice header and its entry points, SEI,
+ * NAL framing, emulation prevention -- the caller writes the entry points from the sizes and adds, per substream, the number of emulation-prevention bytes the NAL
+ * writer will insert into it (TEncGOP.cpp:1673: getNumberOfWrittenBits + (countStartCodeEmulations << 3)).
+ * Refused before anything is enqueued, HOP_ERR_ARG: malformed partition data (the checks of hop_decode_frame; merge index above 4, predictor index outside 0..1, a skipped
+ * CU that is not a merged 2Nx2N CU without residual, a chroma direction outside the CU's allowed ones), a host level beyond 16 bits, an SAO parameter out of range or a
+ * merge without its candidate, sao_coded and the flags disagreeing, a sharded context; HOP_ERR_STATE: levels == NULL with nothing resident.
+ * out_capacity is a hard bound: no byte is stored at or past out + out_capacity.  When the substreams do not fit the call returns HOP_ERR_ARG and *n_substreams holds the
+ * NUMBER OF BYTES NEEDED instead (out's contents are then unspecified, substream_bytes holds the true sizes); hop_last_error says so too.  Resident or host levels that
+ * contradict the partition data (a coded block without a level) give HOP_ERR_ARG as well, found on the device.
+ * Three launches (csrc/k_entropy.hip; hop_profile_* times the first two as HOP_K_ENTROPY_CTX / HOP_K_ENTROPY), one wave per substream: with wpp a context pass first codes the first two CTUs of every row but the last with the bins moving the
+ * context models only, which gives every row the models it starts from (WaveFrontSynchro: TEncSlice.cpp:1351-1376, :1469-1472; a picture one CTU wide has no CTU above
+ * right and every row starts from the initial models); then all substreams of all pictures are coded side by side; a third kernel packs them back to back.  No kernel
+ * waits for another workgroup. */
+typedef struct {
+  int32_t qp;              /* SliceQP: context initialisation */
+  int32_t slice_type;      /* as hop_cabac_init */
+  int32_t wpp;             /* 1: one substream per CTU row, contexts synchronised as TEncSlice.cpp:1351-1376, :1469-1472; 0: one substream */
+  int32_t plain_intra;     /* as hop_enc_params.plain_intra (goes with slice_type 2) */
+  int32_t sao_luma, sao_chroma;   /* slice_sao_luma_flag / slice_sao_chroma_flag; both 0: no SAO syntax */
+  int32_t mi_size;         /* as hop_enc_params.mi_size; the slice data's syntax does not depend on it (the merge list keeps five entries): checked, not read */
+} hop_slice_data_params;
+int hop_slice_data_write(hop_ctx* ctx, const hop_slice_data_params* params, const hop_cu_part* parts, const int32_t* levels, const hop_sao_param* sao_coded,
+                         uint8_t* out, size_t out_capacity, uint32_t* substream_bytes, int32_t* n_substreams);
+/* host only: the same walk and coder compiled for the host (host/hop_entropy.cpp from csrc/k_entropy_dev.inl), one picture, levels required: the yardstick of the device
+ * entry and what the CPU tests drive -- not a CPU path of the library.  Same outputs, refusals and overflow report (no error text: there is no context). */
+int hop_slice_data_write_host(int pic_w, int pic_h, int bit_depth, const hop_slice_data_params* params, const hop_cu_part* parts, const int32_t* levels,
+                              const hop_sao_param* sao_coded, uint8_t* out, size_t out_capacity, uint32_t* substream_bytes, int32_t* n_substreams);
 /* ---- profiling (bench.py roofline): HIP events around every kernel launch on the context stream ---- */
 #define HOP_K_SS_SEARCH 0
 #define HOP_K_FRAC      1
@@ -783,7 +825,9 @@ int hop_sao_reconstruct_params(int n_ctu, int ctus_per_row, int bit_depth, const
 #define HOP_K_WALK_INTER 12   /* + (log2 CU size - 3): the SS/GT candidate walk of csrc/k_walk.inl, one kernel per candidate, by CU size 8 / 16 / 32 / 64 */
 #define HOP_K_WALK_INTRA 16   /* + (log2 CU size - 3): the intra 2Nx2N candidate walk by CU size */
 #define HOP_K_WALK_INTRA_NXN 20   /* the intra NxN candidate walk (8x8 CUs) */
-#define HOP_K_COUNT     21
+#define HOP_K_ENTROPY_CTX 21  /* hop_slice_data_write: the context pass (units: CTUs walked) */
+#define HOP_K_ENTROPY   22    /* hop_slice_data_write: the coding pass (units: CTUs) */
+#define HOP_K_COUNT     23
 int hop_profile_enable(hop_ctx* ctx, int on);
 /* waits for the stream, then reports launches, summed kernel time and units (PUs/CUs/jobs) since the last reset */
 int hop_profile_read(hop_ctx* ctx, int kernel, uint64_t* launches, double* total_ms, uint64_t* units);
