@@ -123,6 +123,31 @@ class DecParams(ctypes.Structure):       # hop_dec_params
 
 
 HOP_K_ENTROPY_CTX, HOP_K_ENTROPY = 21, 22          # hop_profile_read ids of hop_slice_data_write's context pass and coding pass
+HOP_K_PARSE = 23                                   # ... and of hop_slice_data_parse's launches
+
+
+PARSE_GUARD = 256   # bytes behind each output of the slice-data parser that must come back untouched
+
+
+def _parse_io(n, data, sizes, with_levels, with_sao):
+    """the parser's input as an exact-length copy, its outputs with PARSE_GUARD bytes of 0xA5 behind each"""
+    data = np.frombuffer(bytes(data), np.uint8).copy() if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, np.uint8).copy()
+    sizes = np.ascontiguousarray(sizes, np.uint32)
+    assert int(sizes.astype(np.uint64).sum()) == data.size, "the substream sizes do not add up to the data"
+    if data.size == 0:
+        data = np.zeros(1, np.uint8)
+    out = [np.full(nbytes + PARSE_GUARD, 0xA5, np.uint8) if on else None
+           for nbytes, on in ((n * 256 * CU_PART_DTYPE.itemsize, True), (n * 6144 * 4, with_levels), (n * 3 * SAO_PARAM_DTYPE.itemsize, with_sao))]
+    return data, sizes, out
+
+
+def _parse_out(n, out, who):
+    for b in out:
+        assert b is None or np.all(b[-PARSE_GUARD:] == 0xA5), who + " stored past an output"
+    parts = out[0][:-PARSE_GUARD].view(CU_PART_DTYPE).reshape(n, 256)
+    levels = None if out[1] is None else out[1][:-PARSE_GUARD].view(np.int32).reshape(n, 6144)
+    sao = None if out[2] is None else out[2][:-PARSE_GUARD].view(SAO_PARAM_DTYPE).reshape(n, 3)
+    return parts, levels, sao
 
 
 class SliceDataParams(ctypes.Structure):   # hop_slice_data_params
@@ -453,6 +478,25 @@ class Context:
         sizes = sizes[:self.pictures * nsub.value]
         return buf[:int(sizes.sum())].tobytes(), sizes, nsub.value
 
+    def slice_data_parse(self, data, sizes, n_substreams=None, qp=32, slice_type=3, wpp=0, plain_intra=0, sao_luma=1, sao_chroma=1, mi_size=16, want_levels=True):
+        """hop_slice_data_parse: data (bytes) and sizes (uint32) as slice_data_write returned them -> (parts (n_ctu, 256) CU_PART_DTYPE, levels (n_ctu, 6144) int32 or None,
+        sao_coded (n_ctu, 3) or None when both SAO flags are 0).  n_substreams: per picture (default: the CTU rows with wpp, 1 without).  The outputs have guard bytes
+        behind them that must come back untouched (asserted).  An error raises HopError with .code; .outputs holds what was parsed."""
+        n = self._n_ctu()
+        sao_on = bool(sao_luma or sao_chroma)
+        data, sizes, out = _parse_io(n, data, sizes, want_levels, sao_on)
+        if n_substreams is None:
+            n_substreams = (self.sub_h + 63) // 64 if wpp else 1
+        p = SliceDataParams(qp, slice_type, wpp, plain_intra, sao_luma, sao_chroma, mi_size)
+        self.L.hop_slice_data_parse.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int32] + [ctypes.c_void_p] * 3
+        r = self.L.hop_slice_data_parse(self.h, ctypes.byref(p), data.ctypes.data, sizes.ctypes.data, n_substreams, *[None if b is None else b.ctypes.data for b in out])
+        res = _parse_out(n, out, "hop_slice_data_parse")
+        if r != 0:
+            e = HopError("hop_slice_data_parse: %d %s" % (r, self.L.hop_last_error(self.h).decode()))
+            e.code = r; e.outputs = res
+            raise e
+        return res
+
     def profile(self, on=None, reset=False, read=None):
         """hop_profile_enable / hop_profile_reset / hop_profile_read: on: switch the HIP events around the launches on or off; reset: clear the sums; read: a HOP_K_* id ->
         (launches, total ms, units) since the last reset"""
@@ -720,6 +764,26 @@ def slice_data_write_host(W, H, parts, levels, sao_coded=None, bit_depth=8, qp=3
         raise e
     sizes = sizes[:nsub.value]
     return buf[:int(sizes.sum())].tobytes(), sizes, nsub.value
+
+
+def slice_data_parse_host(W, H, data, sizes, n_substreams=None, bit_depth=8, qp=32, slice_type=3, wpp=0, plain_intra=0, sao_luma=1, sao_chroma=1, mi_size=16, want_levels=True,
+                          lib=None):
+    """hop_slice_data_parse_host: the host build of the slice-data parser (the yardstick of Context.slice_data_parse), one picture, no device.  Returns (parts, levels, sao_coded)
+    as the device entry; HopError (.code, .outputs) likewise."""
+    L = lib or load()
+    n = ((W + 63) // 64) * ((H + 63) // 64)
+    data, sizes, out = _parse_io(n, data, sizes, want_levels, bool(sao_luma or sao_chroma))
+    if n_substreams is None:
+        n_substreams = (H + 63) // 64 if wpp else 1
+    p = SliceDataParams(qp, slice_type, wpp, plain_intra, sao_luma, sao_chroma, mi_size)
+    L.hop_slice_data_parse_host.argtypes = [ctypes.c_int] * 3 + [ctypes.c_void_p] * 3 + [ctypes.c_int32] + [ctypes.c_void_p] * 3
+    r = L.hop_slice_data_parse_host(W, H, bit_depth, ctypes.byref(p), data.ctypes.data, sizes.ctypes.data, n_substreams, *[None if b is None else b.ctypes.data for b in out])
+    res = _parse_out(n, out, "hop_slice_data_parse_host")
+    if r != 0:
+        e = HopError("hop_slice_data_parse_host: %d" % r)
+        e.code = r; e.outputs = res
+        raise e
+    return res
 
 
 def decode_footprint(W, H, job, lib=None):

@@ -801,7 +801,8 @@ typedef struct {
   int32_t wpp;             /* 1: one substream per CTU row, contexts synchronised as TEncSlice.cpp:1351-1376, :1469-1472; 0: one substream */
   int32_t plain_intra;     /* as hop_enc_params.plain_intra (goes with slice_type 2) */
   int32_t sao_luma, sao_chroma;   /* slice_sao_luma_flag / slice_sao_chroma_flag; both 0: no SAO syntax */
-  int32_t mi_size;         /* as hop_enc_params.mi_size; the slice data's syntax does not depend on it (the merge list keeps five entries): checked, not read */
+  int32_t mi_size;         /* as hop_enc_params.mi_size; the slice data's syntax does not depend on it (the merge list keeps five entries): the writer checks it and does not read
+                              it; hop_slice_data_parse READS it: the micro-image merge and AMVP candidates are derived with it (1..4096 in the HOP configuration) */
 } hop_slice_data_params;
 int hop_slice_data_write(hop_ctx* ctx, const hop_slice_data_params* params, const hop_cu_part* parts, const int32_t* levels, const hop_sao_param* sao_coded,
                          uint8_t* out, size_t out_capacity, uint32_t* substream_bytes, int32_t* n_substreams);
@@ -809,6 +810,53 @@ int hop_slice_data_write(hop_ctx* ctx, const hop_slice_data_params* params, cons
  * entry and what the CPU tests drive -- not a CPU path of the library.  Same outputs, refusals and overflow report (no error text: there is no context). */
 int hop_slice_data_write_host(int pic_w, int pic_h, int bit_depth, const hop_slice_data_params* params, const hop_cu_part* parts, const int32_t* levels,
                               const hop_sao_param* sao_coded, uint8_t* out, size_t out_capacity, uint32_t* substream_bytes, int32_t* n_substreams);
+/* ---- the entropy decoder: a picture's slice data parsed on the device (the mirror image of hop_slice_data_write) ---- */
+/* replaces: the parsing half of TDecSlice::decompressSlice (TLibDecoder/TDecSlice.cpp:108-380: the CTU loop, the SAO parameters :312-345, the WaveFrontSynchro load and
+ * store of the context models :196-262, :371, the end_of_substream bin :358-366), TDecCu::decodeCU / xDecodeCU / xFinishDecodeCU / xDecodeSliceEnd (TDecCu.cpp:122-380),
+ * TDecEntropy::decodePUWise :160-287, decodeMVPIdxPU :363-433, xDecodeTransform :453-646, decodeCoeff :665-693, the TDecSbac parsers (TDecSbac.cpp: parseSplitFlag :544,
+ * parseSkipFlag :425, parsePredMode :652, parsePartSize :571, parseMergeFlag / Index :464 / :497, parseGTFlag :484, parseMvd :838, parseGT :903, parseMVPIdx :533,
+ * parseIntraDirLumaAng :670, parseIntraDirChroma :735, parseQtRootCbf :1370, parseQtCbf :1428, parseTransformSubdivFlag :1356, parseLastSignificantXY :1497,
+ * parseCoeffNxN :1556-1830, parseSAOBlkParam :1906 with :1835-1901), the arithmetic decoder TDecBinCABAC (TDecBinCoderCABAC.cpp: start :65, finish :75, decodeBin :100,
+ * decodeBinEP :146, decodeBinsEP :165, decodeBinTrm :212) and what a decoder derives instead of reading: TComDataCU::getIntraDirLumaPredictor, getAllowedChromaDir,
+ * getInterMergeCandidates (TComDataCU.cpp:2761-3204, with the micro-image candidates :2620-2748) and fillMvpCand (:3297-3478), in the configuration of
+ * hop_slice_data_write (I slices with plain_intra at 8 and 10 bit, the HOP ISS slice).
+ * data: the RBSP bytes of the substreams of one slice per picture, back to back, BEFORE emulation prevention -- exactly what hop_slice_data_write returns;
+ * substream_bytes[i]: the length of substream i, as the caller read it from the slice header's entry points (less the emulation-prevention bytes it removed);
+ * n_substreams: per picture, the CTU rows with wpp, 1 without.  A stacked context parses its pictures one after the other in data, substream_bytes and the outputs.
+ * Outputs, in the layouts hop_decode_frame, hop_deblock_frame, hop_sao_reconstruct_params and hop_slice_data_write take: parts 256 per CTU, levels 6144 per CTU (may be
+ * NULL: parsed and dropped), sao_coded 3 per CTU (non-NULL iff an SAO flag is set).  Not parsed here: parameter sets, the slice header and its entry points, SEI, NAL
+ * framing, emulation prevention -- the caller's.  Call sequence of a decode: hop_slice_data_parse -> hop_decode_frame -> hop_deblock_frame ->
+ * hop_sao_reconstruct_params -> hop_sao_apply.
+ * What the stream does not carry, and what the parser stores there (hop_encode_frame's values, so that parts parsed from a stream it wrote compare equal):
+ *   a unit outside the picture (partial CTU), or never reached because its substream stopped: pred_mode 15, part_size 15, ref_idx -1, mvp_idx -1, mvp_num -1,
+ *     luma_dir 1 (DC), everything else 0; depth: the depth of the quadtree node that lies outside (0 for a unit never reached);
+ *   an intra CU: skip, merge_flag, merge_idx, gt_flag, inter_dir, mv, mvd, gt 0; ref_idx, mvp_idx, mvp_num -1;
+ *   an SS / GT CU: luma_dir 1, chroma_dir 0; a skipped CU or one without residual: tr_idx 0, cbf 0, tskip 0;
+ *   a merged or skipped PU: mv, ref_idx, inter_dir from the merge list; mvd 0, mvp_idx -1, mvp_num -1, gt_flag 0, gt 0;
+ *   an unmerged PU: mv = AMVP candidate[mvp_idx] + mvd, ref_idx 0, inter_dir 1, merge_idx 0, mvp_num 2; gt all 0 without GT; with GT the fourth corner gt[6..7] =
+ *     corner 0 - corner 1 + corner 2, as parseGT leaves it;
+ *   gt_flag: the PU's flag on ALL units of the PU.  The stream carries the flag of the PU's first unit; hop_encode_frame's parts may differ on the others (the
+ *     reference's encoder clears the flag of the unit with the PU's NUMBER, TEncSearch.cpp:3721) -- no consumer reads them;
+ *   tskip: the flag of a coded 4x4 block (a chroma block's on the four units of its 8x8 node), 0 elsewhere; cbf: bit t on every unit of a transform node of depth t;
+ *   sao_coded: a component that is off, or switched off in the slice, all 0; a merged record: mode 2, type 0 left / 1 above, and the band position and offsets of the
+ *     candidate as reconstructBlkSAOParam resolves them (what hop_sao_frame returns there; neither the stream nor any consumer carries them).
+ * Bounds: no byte at or past the end of a substream is read (the decoder sees zeros there); every loop is bounded by the picture's geometry or a constant; unary and
+ * Exp-Golomb prefixes are capped; levels are clipped to 16 bits; vector components beyond int16_t, a prefix beyond its cap and a last position outside its block stop
+ * the substream.  Whatever the bytes, nothing is stored outside the outputs, and a substream that stops leaves its remaining units as "never reached".
+ * Refused before anything is enqueued, HOP_ERR_ARG: NULL or inconsistent arguments, a sharded context, n_substreams other than the picture's, an empty substream, sizes
+ * that overflow, params hop_slice_data_write refuses, mi_size outside 1..4096 in the HOP configuration.  Found on the device, HOP_ERR_ARG as well, hop_last_error naming
+ * substream, CTU and kind: the stream ran past the substream's end; a value out of range; a terminating bin with the wrong value, the stop pattern missing, or a consumed
+ * length (as TDecBinCABAC::finish and readOutTrailingBits count it) other than substream_bytes[i].  The outputs then hold what was parsed; the context stays usable.
+ * Launches (csrc/k_parse.hip; hop_profile_* times them as HOP_K_PARSE): one wave per substream, lane 0 parsing.  With wpp the rows advance in diagonal launches -- launch d
+ * parses CTU d - 2 r of every row r that has one, of all pictures side by side: wctu + 2 (hctu - 1) launches -- because the CTU at (r, c) needs the context models, depths,
+ * skip flags and vectors of row r - 1 up to column c + 1; no kernel waits for another workgroup.  Without wpp one launch, one wave per picture.
+ * The resident levels of hop_encode_frame and their validity are left untouched. */
+int hop_slice_data_parse(hop_ctx* ctx, const hop_slice_data_params* params, const uint8_t* data, const uint32_t* substream_bytes, int32_t n_substreams,
+                         hop_cu_part* parts, int32_t* levels, hop_sao_param* sao_coded);
+/* host only: the same parser compiled for the host (host/hop_parse.cpp from csrc/k_parse_dev.inl), one picture: the yardstick of the device entry and what the CPU
+ * tests and tools/slicedata_parse_check.cpp drive -- not a CPU path of the library.  Same outputs and refusals (no error text: there is no context). */
+int hop_slice_data_parse_host(int pic_w, int pic_h, int bit_depth, const hop_slice_data_params* params, const uint8_t* data, const uint32_t* substream_bytes,
+                              int32_t n_substreams, hop_cu_part* parts, int32_t* levels, hop_sao_param* sao_coded);
 /* ---- profiling (bench.py roofline): HIP events around every kernel launch on the context stream ---- */
 #define HOP_K_SS_SEARCH 0
 #define HOP_K_FRAC      1
@@ -827,7 +875,8 @@ int hop_slice_data_write_host(int pic_w, int pic_h, int bit_depth, const hop_sli
 #define HOP_K_WALK_INTRA_NXN 20   /* the intra NxN candidate walk (8x8 CUs) */
 #define HOP_K_ENTROPY_CTX 21  /* hop_slice_data_write: the context pass (units: CTUs walked) */
 #define HOP_K_ENTROPY   22    /* hop_slice_data_write: the coding pass (units: CTUs) */
-#define HOP_K_COUNT     23
+#define HOP_K_PARSE     23    /* hop_slice_data_parse: the launches of the parser (units: CTUs) */
+#define HOP_K_COUNT     24
 int hop_profile_enable(hop_ctx* ctx, int on);
 /* waits for the stream, then reports launches, summed kernel time and units (PUs/CUs/jobs) since the last reset */
 int hop_profile_read(hop_ctx* ctx, int kernel, uint64_t* launches, double* total_ms, uint64_t* units);
