@@ -79,9 +79,13 @@ __global__ __launch_bounds__(256) void k_entropy_pack(const uint8_t* __restrict_
 }
 }  // namespace
 
-extern "C" int hop_slice_data_write(hop_ctx* c, const hop_slice_data_params* p, const hop_cu_part* parts, const int32_t* levels, const hop_sao_param* sao,
-                                    uint8_t* out, size_t out_capacity, uint32_t* substream_bytes, int32_t* n_substreams) {
-  if (!c || !p || !parts || !substream_bytes || !n_substreams || (!out && out_capacity)) return hop_set_err(c, HOP_ERR_ARG, "hop_slice_data_write: bad argument");
+// internal: hop_slice_data_write, and for hop_access_unit_write (csrc/k_stream.hip) the same with the substreams LEFT ON THE DEVICE: with d_packed the packed substreams
+// are not copied to `out` (which may be NULL) but their device address is returned, with `reserve` further bytes of the same scratch allocation behind them (*d_reserve,
+// 256-aligned) -- both valid until the context's scratch area is asked for again
+extern "C" __attribute__((visibility("hidden"))) int hop_ent_write_device(hop_ctx* c, const hop_slice_data_params* p, const hop_cu_part* parts, const int32_t* levels,
+                                                                         const hop_sao_param* sao, uint8_t* out, size_t out_capacity, uint32_t* substream_bytes,
+                                                                         int32_t* n_substreams, size_t reserve, const uint8_t** d_packed, uint8_t** d_reserve) {
+  if (!c || !p || !parts || !substream_bytes || !n_substreams || (!out && out_capacity && !d_packed)) return hop_set_err(c, HOP_ERR_ARG, "hop_slice_data_write: bad argument");
   if (c->shard_world > 1) return hop_set_err(c, HOP_ERR_ARG, "hop_slice_data_write: a sharded context writes no slice data");
   if (!levels && !(c->coefpic && c->levels_valid))
     return hop_set_err(c, HOP_ERR_STATE, "hop_slice_data_write: levels == NULL, but the context holds no levels of a finished hop_encode_frame (none has run, the last one failed, or hop_decode_frame has replaced the picture since: pass the levels)");
@@ -103,7 +107,7 @@ extern "C" int hop_slice_data_write(hop_ctx* c, const hop_slice_data_params* p, 
   auto seg = [&](size_t bytes) { const size_t at = (end + 255) & ~(size_t)255; end = at + bytes; return at; };
   const size_t o_parts = seg(sizeof(hop_cu_part) * 256 * (size_t)n * n_pic), o_levels = seg(levels ? sizeof(int32_t) * 6144 * (size_t)n * n_pic : 0),
                o_sao = seg(sao ? sizeof(hop_sao_param) * 3 * (size_t)n * n_pic : 0), o_init = seg(EN_STATES), o_entry = seg((size_t)n_pic * hctu * EN_STATES),
-               o_sizes = seg(sizeof(uint32_t) * 2 * (size_t)n_blocks), o_slabs = seg(slab_stride * n_blocks + 256), o_packed = seg(packed + 256);
+               o_sizes = seg(sizeof(uint32_t) * 2 * (size_t)n_blocks), o_slabs = seg(slab_stride * n_blocks + 256), o_packed = seg(packed + 256), o_reserve = seg(reserve);
   void* buf; r = hop_scratch(c, end, &buf); if (r) return r;
   char* b = (char*)buf;
   HIPCHK(c, hipSetDevice(c->device));
@@ -149,7 +153,13 @@ extern "C" int hop_slice_data_write(hop_ctx* c, const hop_slice_data_params* p, 
     return hop_set_err(c, HOP_ERR_ARG, "hop_slice_data_write: the slice data takes %zu bytes, out_capacity is %zu", total, out_capacity);
   }
   for (int i = 0; i < n_blocks; i++) if ((sz[n_blocks + i] & 1u) || sz[i] > slab_limit) return hop_set_err(c, HOP_ERR_DEVICE, "hop_slice_data_write: substream %d outgrew its slab (%u bytes)", i, sz[i]);
-  if (total) HIPCHK(c, hipMemcpy(out, b + o_packed, total, hipMemcpyDeviceToHost));
+  if (d_packed) { *d_packed = (const uint8_t*)(b + o_packed); *d_reserve = (uint8_t*)(b + o_reserve); }
+  else if (total) HIPCHK(c, hipMemcpy(out, b + o_packed, total, hipMemcpyDeviceToHost));
   *n_substreams = n_sub;
   return HOP_OK;
+}
+
+extern "C" int hop_slice_data_write(hop_ctx* c, const hop_slice_data_params* p, const hop_cu_part* parts, const int32_t* levels, const hop_sao_param* sao,
+                                    uint8_t* out, size_t out_capacity, uint32_t* substream_bytes, int32_t* n_substreams) {
+  return hop_ent_write_device(c, p, parts, levels, sao, out, out_capacity, substream_bytes, n_substreams, 0, nullptr, nullptr);
 }

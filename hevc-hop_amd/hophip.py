@@ -124,6 +124,7 @@ class DecParams(ctypes.Structure):       # hop_dec_params
 
 HOP_K_ENTROPY_CTX, HOP_K_ENTROPY = 21, 22          # hop_profile_read ids of hop_slice_data_write's context pass and coding pass
 HOP_K_PARSE = 23                                   # ... and of hop_slice_data_parse's launches
+HOP_K_ESCAPE, HOP_K_PICHASH = 24, 25               # ... of the emulation-prevention launches and the checksum pass (hop_access_unit_write, hop_rbsp_escape, hop_picture_hash)
 
 
 PARSE_GUARD = 256   # bytes behind each output of the slice-data parser that must come back untouched
@@ -155,6 +156,10 @@ class SliceDataParams(ctypes.Structure):   # hop_slice_data_params
                 ("sao_chroma", ctypes.c_int32), ("mi_size", ctypes.c_int32)]
 
 
+class StreamParams(ctypes.Structure):   # hop_stream_params
+    _fields_ = [("slice", SliceDataParams), ("poc", ctypes.c_int32), ("parameter_sets", ctypes.c_int32), ("hash", ctypes.c_int32)]
+
+
 _I16P = ctypes.POINTER(ctypes.c_int16)
 
 
@@ -169,7 +174,7 @@ MIRRORS = {"hop_pu_job": PU_JOB_DTYPE, "hop_pu_result": PU_RESULT_DTYPE, "hop_pr
            "hop_rqt_result": RQT_RESULT_DTYPE, "hop_cu_syntax": CU_SYNTAX_DTYPE, "hop_intra_cu_syntax": INTRA_CU_SYNTAX_DTYPE, "hop_intra_rqt_opt": INTRA_RQT_OPT_DTYPE,
            "hop_intra_search_job": INTRA_SEARCH_JOB_DTYPE, "hop_intra_search_result": INTRA_SEARCH_RESULT_DTYPE, "hop_cu_part": CU_PART_DTYPE, "hop_enc_params": EncParams,
            "hop_deblock_params": DeblockParams, "hop_sao_param": SAO_PARAM_DTYPE, "hop_sao_params": SaoParams, "hop_dec_params": DecParams,
-           "hop_slice_data_params": SliceDataParams}
+           "hop_slice_data_params": SliceDataParams, "hop_stream_params": StreamParams}
 
 
 def mirror_size(m):
@@ -478,6 +483,47 @@ class Context:
         sizes = sizes[:self.pictures * nsub.value]
         return buf[:int(sizes.sum())].tobytes(), sizes, nsub.value
 
+    def access_unit_write(self, parts, levels=None, sao_coded=None, qp=32, slice_type=3, wpp=0, plain_intra=0, sao_luma=None, sao_chroma=None, mi_size=16, poc=0,
+                          parameter_sets=1, hash=1, capacity=None, guard=0):
+        """hop_access_unit_write: the Annex B bytes of one access unit per picture of the context -- parts, levels (None = resident) and sao_coded as slice_data_write;
+        poc 0: the IDR picture; parameter_sets 1: VPS, SPS, PPS in front; hash: 0 none, 1 MD5, 3 checksum of the resident reconstruction in a suffix SEI.  Returns (bytes,
+        sizes per picture).  capacity / guard as slice_data_write; an output that does not fit raises HopError with .needed = the bytes it takes."""
+        parts = np.ascontiguousarray(parts, CU_PART_DTYPE)
+        n = self._n_ctu()
+        assert parts.size == n * 256
+        if levels is not None:
+            levels = np.ascontiguousarray(levels, np.int32); assert levels.size == n * 6144
+        if sao_coded is not None:
+            sao_coded = np.ascontiguousarray(sao_coded, SAO_PARAM_DTYPE); assert sao_coded.size == n * 3
+        on = 0 if sao_coded is None else 1
+        p = StreamParams(SliceDataParams(qp, slice_type, wpp, plain_intra, on if sao_luma is None else sao_luma, on if sao_chroma is None else sao_chroma, mi_size),
+                         poc, parameter_sets, hash)
+        cap = n * 16384 + 1024 * self.pictures if capacity is None else capacity
+        buf = np.full(cap + guard, 0xA5, np.uint8)
+        sizes = (ctypes.c_size_t * self.pictures)()
+        self.L.hop_access_unit_write.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_size_t, ctypes.c_void_p]
+        r = self.L.hop_access_unit_write(self.h, ctypes.byref(p), parts.ctypes.data, None if levels is None else levels.ctypes.data,
+                                         None if sao_coded is None else sao_coded.ctypes.data, buf.ctypes.data, cap, sizes)
+        assert np.all(buf[cap:] == 0xA5), "hop_access_unit_write stored past out_capacity"
+        if r != 0:
+            e = HopError("hop_access_unit_write: %d %s" % (r, self.L.hop_last_error(self.h).decode()))
+            e.code = r; e.needed = int(sizes[0])
+            raise e
+        sizes = np.array(list(sizes), np.uint64)
+        return buf[:int(sizes.sum())].tobytes(), sizes
+
+    def rbsp_escape(self, data, segments=None, capacity=None, guard=0, want_counts=True):
+        """hop_rbsp_escape: emulation prevention over the concatenation of the segments (byte lengths; default: one) of data, on the device.  Returns (bytes, per-segment
+        counts of the segments alone or None).  An output that does not fit raises HopError with .needed."""
+        return _rbsp_escape(self.L, self.L.hop_rbsp_escape, self.h, data, segments, capacity, guard, want_counts)
+
+    def picture_hash(self, method):
+        """hop_picture_hash: the decoded-picture hash of the resident reconstruction, (pictures, 3, 16) uint8 -- method 1 MD5, 3 checksum (4 bytes, then zeros)"""
+        d = np.zeros((self.pictures, 3, 16), np.uint8)
+        self.L.hop_picture_hash.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        self._chk(self.L.hop_picture_hash(self.h, method, d.ctypes.data), "hop_picture_hash")
+        return d
+
     def slice_data_parse(self, data, sizes, n_substreams=None, qp=32, slice_type=3, wpp=0, plain_intra=0, sao_luma=1, sao_chroma=1, mi_size=16, want_levels=True):
         """hop_slice_data_parse: data (bytes) and sizes (uint32) as slice_data_write returned them -> (parts (n_ctu, 256) CU_PART_DTYPE, levels (n_ctu, 6144) int32 or None,
         sao_coded (n_ctu, 3) or None when both SAO flags are 0).  n_substreams: per picture (default: the CTU rows with wpp, 1 without).  The outputs have guard bytes
@@ -764,6 +810,70 @@ def slice_data_write_host(W, H, parts, levels, sao_coded=None, bit_depth=8, qp=3
         raise e
     sizes = sizes[:nsub.value]
     return buf[:int(sizes.sum())].tobytes(), sizes, nsub.value
+
+
+def _rbsp_escape(L, fn, ctx, data, segments, capacity, guard, want_counts):
+    data = bytes(data)
+    a = np.frombuffer(data, np.uint8) if data else np.zeros(1, np.uint8)
+    seg = np.asarray([len(data)] if segments is None else segments, np.uint32)
+    cap = len(data) * 3 // 2 + 2 if capacity is None else capacity
+    buf = np.full(cap + guard, 0xA5, np.uint8); n = ctypes.c_size_t(0); cnt = np.zeros(max(1, len(seg)), np.uint32)
+    tail = [a.ctypes.data, seg.ctypes.data, len(seg), buf.ctypes.data, cap, ctypes.byref(n), cnt.ctypes.data if want_counts else None]
+    fn.argtypes = ([ctypes.c_void_p] if ctx is not None else []) + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
+    r = fn(*(([ctx] if ctx is not None else []) + tail))
+    assert np.all(buf[cap:] == 0xA5), "hop_rbsp_escape stored past out_capacity"
+    if r != 0:
+        e = HopError("hop_rbsp_escape: %d %s" % (r, L.hop_last_error(ctx).decode() if ctx is not None else ""))
+        e.code = r; e.needed = n.value
+        raise e
+    return buf[:n.value].tobytes(), (cnt[:len(seg)] if want_counts else None)
+
+
+def rbsp_escape_host(data, segments=None, capacity=None, guard=0, want_counts=True, lib=None):
+    """hop_rbsp_escape_host: the sequential rule on the host (the yardstick of Context.rbsp_escape); same results and HopError"""
+    L = lib or load()
+    return _rbsp_escape(L, L.hop_rbsp_escape_host, None, data, segments, capacity, guard, want_counts)
+
+
+def parameter_sets_write(W, H, bit_depth=8, qp=32, slice_type=3, wpp=0, plain_intra=0, sao=1, mi_size=16, lib=None):
+    """hop_parameter_sets_write: the VPS, SPS and PPS NAL units with their start codes, as bytes"""
+    L = lib or load()
+    p = StreamParams(SliceDataParams(qp, slice_type, wpp, plain_intra, sao, sao, mi_size), 0, 1, 0)
+    buf = np.zeros(256, np.uint8); n = ctypes.c_size_t(0)
+    L.hop_parameter_sets_write.argtypes = [ctypes.c_int] * 3 + [ctypes.c_void_p] * 2 + [ctypes.c_size_t, ctypes.c_void_p]
+    r = L.hop_parameter_sets_write(W, H, bit_depth, ctypes.byref(p), buf.ctypes.data, buf.size, ctypes.byref(n))
+    if r != 0:
+        raise HopError("hop_parameter_sets_write: %d" % r)
+    return buf[:n.value].tobytes()
+
+
+def access_unit_write_host(W, H, parts, levels, sao_coded=None, rec=None, bit_depth=8, qp=32, slice_type=3, wpp=0, plain_intra=0, sao_luma=None, sao_chroma=None, mi_size=16,
+                           poc=0, parameter_sets=1, hash=1, capacity=None, lib=None):
+    """hop_access_unit_write_host: the host build of the outer layer over slice_data_write_host (the yardstick of Context.access_unit_write), one picture, no device; rec: the
+    final reconstruction planes [Y, Cb, Cr], None iff hash == 0.  Returns the access unit's bytes; HopError (.code, .needed) as the device entry."""
+    L = lib or load()
+    n = ((W + 63) // 64) * ((H + 63) // 64)
+    parts = np.ascontiguousarray(parts, CU_PART_DTYPE); levels = np.ascontiguousarray(levels, np.int32)
+    assert parts.size == n * 256 and levels.size == n * 6144
+    if sao_coded is not None:
+        sao_coded = np.ascontiguousarray(sao_coded, SAO_PARAM_DTYPE); assert sao_coded.size == n * 3
+    on = 0 if sao_coded is None else 1
+    p = StreamParams(SliceDataParams(qp, slice_type, wpp, plain_intra, on if sao_luma is None else sao_luma, on if sao_chroma is None else sao_chroma, mi_size),
+                     poc, parameter_sets, hash)
+    planes = None
+    if rec is not None:
+        keep = [np.ascontiguousarray(a, np.int16) for a in rec]
+        planes = (ctypes.c_void_p * 3)(*[a.ctypes.data for a in keep])
+    cap = n * 16384 + 1024 if capacity is None else capacity
+    buf = np.zeros(cap, np.uint8); size = ctypes.c_size_t(0)
+    L.hop_access_unit_write_host.argtypes = [ctypes.c_int] * 3 + [ctypes.c_void_p] * 6 + [ctypes.c_size_t, ctypes.c_void_p]
+    r = L.hop_access_unit_write_host(W, H, bit_depth, ctypes.byref(p), parts.ctypes.data, levels.ctypes.data, None if sao_coded is None else sao_coded.ctypes.data, planes,
+                                     buf.ctypes.data, cap, ctypes.byref(size))
+    if r != 0:
+        e = HopError("hop_access_unit_write_host: %d" % r)
+        e.code = r; e.needed = size.value
+        raise e
+    return buf[:size.value].tobytes()
 
 
 def slice_data_parse_host(W, H, data, sizes, n_substreams=None, bit_depth=8, qp=32, slice_type=3, wpp=0, plain_intra=0, sao_luma=1, sao_chroma=1, mi_size=16, want_levels=True,

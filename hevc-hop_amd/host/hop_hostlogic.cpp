@@ -334,6 +334,7 @@ int hop_sizeof(const char* name) {
   S(hop_sao_params);
   S(hop_dec_params);
   S(hop_slice_data_params);
+  S(hop_stream_params);
 #undef S
   return -1;
 }

@@ -783,8 +783,8 @@ int hop_sao_reconstruct_params(int n_ctu, int ctus_per_row, int bit_depth, const
  * out receives the substreams back to back, in order; each is RBSP bytes BEFORE emulation prevention and complete: the terminating bin 1, TEncBinCABAC::finish, then the
  * byte alignment of slice_data (TEncGOP.cpp:1653-1662).  substream_bytes[i] is the length of substream i, *n_substreams their number per picture (wpp: the CTU rows; else
  * 1); a stacked context writes its pictures one after the other, n_substreams sizes each.  Not written here: VPS / SPS / PPS, the slice header and its entry points, SEI,
- * NAL framing, emulation prevention -- the caller writes the entry points from the sizes and adds, per substream, the number of emulation-prevention bytes the NAL
- * writer will insert into it (TEncGOP.cpp:1673: getNumberOfWrittenBits + (countStartCodeEmulations << 3)).
+ * NAL framing, emulation prevention -- hop_access_unit_write (below) writes them around this entry's bytes; the entry-point arithmetic (per substream its size plus the
+ * emulation-prevention bytes the NAL writer inserts into it, TEncGOP.cpp:1673: getNumberOfWrittenBits + (countStartCodeEmulations << 3)) lives there.
  * Refused before anything is enqueued, HOP_ERR_ARG: malformed partition data (the checks of hop_decode_frame; merge index above 4, predictor index outside 0..1, a skipped
  * CU that is not a merged 2Nx2N CU without residual, a chroma direction outside the CU's allowed ones), a host level beyond 16 bits, an SAO parameter out of range or a
  * merge without its candidate, sao_coded and the flags disagreeing, a sharded context; HOP_ERR_STATE: levels == NULL with nothing resident.
@@ -857,6 +857,56 @@ int hop_slice_data_parse(hop_ctx* ctx, const hop_slice_data_params* params, cons
  * tests and tools/slicedata_parse_check.cpp drive -- not a CPU path of the library.  Same outputs and refusals (no error text: there is no context). */
 int hop_slice_data_parse_host(int pic_w, int pic_h, int bit_depth, const hop_slice_data_params* params, const uint8_t* data, const uint32_t* substream_bytes,
                               int32_t n_substreams, hop_cu_part* parts, int32_t* levels, hop_sao_param* sao_coded);
+/* ---- the stream around the slice data: a picture's complete access unit (Annex B) ---- */
+/* What the outer layer varies with: the slice-data parameters, the picture's place in its all-intra sequence, and what goes around the slice NAL unit.  Everything else
+ * the option lists of the HOP all-intra configuration and of the plain intra configurations (main at 8 bit, main10 at 10 bit) fix is a constant of the writer
+ * (host/hop_stream.cpp names the reference line behind each).  sample_adaptive_offset_enabled_flag of the SPS is sao_luma | sao_chroma. */
+typedef struct {
+  hop_slice_data_params slice;  /* as hop_slice_data_write; slice_type 2 (plain_intra 1) or 3 (the HOP configuration's ISS slice) */
+  int32_t poc;                  /* 0: the IDR picture (NAL type 19) as the reference codes the first picture; > 0: a later picture of the same all-intra sequence
+                                   (IntraPeriod 1, DecodingRefreshType 0, GOPSize 1): NAL type 0 (TRAIL_N) for the ISS slice, 1 (TRAIL_R) for the plain I slice (TEncGOP.cpp:636-643),
+                                   pic_order_cnt_lsb = poc & 255, reference picture set 0 of the SPS; the golden 128x64_2frames shows the ISS form */
+  int32_t parameter_sets;       /* 1: VPS, SPS, PPS in front of the slice NAL unit */
+  int32_t hash;                 /* SEIDecodedPictureHash: 0 none, 1 MD5, 3 checksum; 2 (CRC) is refused with HOP_ERR_ARG */
+} hop_stream_params;
+/* replaces: what TEncGOP::compressGOP does with a coded picture (TLibEncoder/TEncGOP.cpp:1206 ff. the parameter sets, :1641-1680 substream sizes and entry points,
+ * :2810 the slice header's byte alignment, :1794-1809 the hash SEI) through TEncCavlc::codeVPS / codeSPS / codePPS / codePTL / codeProfileTier (TEncCavlc.cpp:156-583,
+ * :939-1000), codeSliceHeader (:585-937), codeTilesWPPEntryPoint (:1002-1070), writeNalUnitHeader and write (NALwrite.cpp:67-153: emulation prevention),
+ * writeRBSPTrailingBits, SEIWriter::xWriteSEIDecodedPictureHash (SEIwrite.cpp:229-255), calcMD5 / calcChecksum (TLibCommon/TComPicYuvMD5.cpp) and the start codes of
+ * writeAnnexB (AnnexBwrite.h): the Annex B bytes of one access unit per picture of the context, a stack's one after the other, au_bytes[p] each.  In order: the parameter
+ * sets if asked for (four-byte start codes), the slice NAL unit (four-byte start code when it is the access unit's first unit, else three), the suffix SEI (type 40,
+ * three-byte start code) if hash != 0.  parts, levels (NULL = resident) and sao_coded are as in hop_slice_data_write, whose refusals apply; the hash is taken from the
+ * reconstruction resident in the context.  Call order: hop_encode_frame -> hop_deblock_frame -> hop_sao_frame (or deblocking alone when both SAO flags are 0) -> this.
+ * entry_point_offset[i] = substream_bytes[i] + the emulation-prevention bytes of substream i ALONE (the reference's rule; a substream ends with its alignment bit and the
+ * header with its own, so no zero run crosses a boundary in a real stream); offset_len_minus1 from the largest offset.
+ * Refused, HOP_ERR_ARG: dimensions that are no multiples of 8, a bit depth other than 8 / 10, slice types other than 2 / 3, hash 2, a sharded context.
+ * out_capacity is a hard bound; when the access units do not fit the call returns HOP_ERR_ARG with the bytes needed (all pictures) in au_bytes[0].
+ * Device work (csrc/k_stream.hip; hop_profile_*: HOP_K_ESCAPE, HOP_K_PICHASH): the slice data stays where hop_slice_data_write's kernels packed it; a count launch gives each
+ * substream's emulation count, the host writes NAL header and slice header from them, and three launches (count, scan, scatter) escape header + substreams into the
+ * finished NAL unit, which one transfer brings to the host.  The checksum is a device pass; MD5 is hashed on the host from the downloaded planes. */
+int hop_access_unit_write(hop_ctx* ctx, const hop_stream_params* params, const hop_cu_part* parts, const int32_t* levels, const hop_sao_param* sao_coded,
+                          uint8_t* out, size_t out_capacity, size_t* au_bytes);
+/* host only, one picture: the same header code and the host escape over hop_slice_data_write_host; rec: the final reconstruction planes (pitch pic_w, pic_w / 2), NULL iff
+ * hash == 0.  The yardstick of the device entry and what the CPU tests drive -- not a CPU path of the library.  On overflow *au_bytes holds the bytes needed. */
+int hop_access_unit_write_host(int pic_w, int pic_h, int bit_depth, const hop_stream_params* params, const hop_cu_part* parts, const int32_t* levels,
+                               const hop_sao_param* sao_coded, const int16_t* const rec[3], uint8_t* out, size_t out_capacity, size_t* au_bytes);
+/* host only, no context: the VPS, SPS and PPS NAL units with their start codes (codeVPS with the fork's vps_holo_extension_flag / vps_holo_microimage_size, codeSPS,
+ * codePPS); *bytes: their length, also when they do not fit (HOP_ERR_ARG). */
+int hop_parameter_sets_write(int pic_w, int pic_h, int bit_depth, const hop_stream_params* params, uint8_t* out, size_t out_capacity, size_t* bytes);
+/* replaces: the emulation prevention of write() (NALwrite.cpp:108-152) over the concatenation of n_segments segments of RBSP bytes (host, back to back in rbsp), the final
+ * 03 behind a trailing 00 included, on the device: three launches, count / scan / scatter.  segment_emulations (may be NULL): per segment what
+ * TComOutputBitstream::countStartCodeEmulations (TComBitStream.cpp:186-216) gives for that segment ALONE.  *out_bytes: the output's length; when it exceeds out_capacity
+ * the call returns HOP_ERR_ARG, *out_bytes still the bytes needed, and nothing is stored at or past out + out_capacity.  An empty segment or no segment: HOP_ERR_ARG. */
+int hop_rbsp_escape(hop_ctx* ctx, const uint8_t* rbsp, const uint32_t* segment_bytes, int32_t n_segments, uint8_t* out, size_t out_capacity, size_t* out_bytes,
+                    uint32_t* segment_emulations);
+/* host only: the same, as the sequential rule; the parameter sets and the SEI are escaped with it */
+int hop_rbsp_escape_host(const uint8_t* rbsp, const uint32_t* segment_bytes, int32_t n_segments, uint8_t* out, size_t out_capacity, size_t* out_bytes,
+                         uint32_t* segment_emulations);
+/* replaces: calcMD5 / calcChecksum (TLibCommon/TComPicYuvMD5.cpp:141-213) over the reconstruction resident in the context: per picture of the context and plane (Y, Cb, Cr)
+ * 16 bytes, MD5 all of them, the checksum its four bytes, most significant first, then zeros.  method 1 (MD5, written from RFC 1321) downloads the planes and hashes on
+ * the host -- MD5 is one dependent chain per plane; method 3 (checksum) is a device pass.  Above 8 bit a sample is hashed as two bytes, low byte first. */
+int hop_picture_hash(hop_ctx* ctx, int method, uint8_t (*digest)[16]);
+
 /* ---- profiling (bench.py roofline): HIP events around every kernel launch on the context stream ---- */
 #define HOP_K_SS_SEARCH 0
 #define HOP_K_FRAC      1
@@ -876,7 +926,9 @@ int hop_slice_data_parse_host(int pic_w, int pic_h, int bit_depth, const hop_sli
 #define HOP_K_ENTROPY_CTX 21  /* hop_slice_data_write: the context pass (units: CTUs walked) */
 #define HOP_K_ENTROPY   22    /* hop_slice_data_write: the coding pass (units: CTUs) */
 #define HOP_K_PARSE     23    /* hop_slice_data_parse: the launches of the parser (units: CTUs) */
-#define HOP_K_COUNT     24
+#define HOP_K_ESCAPE    24    /* hop_rbsp_escape / hop_access_unit_write: the count, scan and scatter launches (units: bytes) */
+#define HOP_K_PICHASH   25    /* hop_picture_hash / hop_access_unit_write: the checksum pass (units: samples) */
+#define HOP_K_COUNT     26
 int hop_profile_enable(hop_ctx* ctx, int on);
 /* waits for the stream, then reports launches, summed kernel time and units (PUs/CUs/jobs) since the last reset */
 int hop_profile_read(hop_ctx* ctx, int kernel, uint64_t* launches, double* total_ms, uint64_t* units);
