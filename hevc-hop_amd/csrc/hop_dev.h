@@ -158,6 +158,7 @@ int hop_launch_ss_search(hop_ctx* c, int n, const hop_pu_job* d_jobs, hop_pu_res
 int hop_launch_frac(hop_ctx* c, int n, const hop_pu_job* d_jobs, hop_pu_result* d_res);
 int hop_launch_gt(hop_ctx* c, int n, const hop_pu_job* d_jobs, hop_pu_result* d_res);
 void hop_launch_size_classes(hop_ctx* c, int n, const hop_pu_job* d_jobs, const hop_pu_result* d_res, void* sc);
+bool hop_me_small_batch(int n);           // the fractional and the GT search take their one-launch form (k_gt_search.hip; HOP_ME_WIDE, read per call)
 int hop_check_pu_jobs(hop_ctx* c, int n, const hop_pu_job* jobs);        // host: the checks of hop_me_search / hop_pred_inter without the transfer (the spine packs its own pinned buffers)
 int hop_check_pred_jobs(hop_ctx* c, int n, const hop_pred_job* jobs);
 int hop_launch_pred(hop_ctx* c, int n, const hop_pred_job* d_jobs);

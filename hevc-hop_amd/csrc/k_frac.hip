@@ -7,8 +7,10 @@
 // for the 9 + 9 candidate phases out of an LDS copy of the (W+8)x(H+8) integer window.
 //
 // One workgroup per PU.  Per stage: 3 horizontally filtered planes (the three x phases of the stage) are
-// built by all 256 threads, then (candidate, 8x8 block) units are dealt round-robin to the 4 waves:
+// built by all threads, then (candidate, 8x8 block) units are dealt round-robin to the NW waves:
 // lane = one sample, vertical 8-tap from LDS, Hadamard across the wave, integer atomicAdd per candidate.
+// Two forms of the launch (hop_launch_frac; hop_me_small_batch in k_gt_search.hip): large batches run the two size
+// classes of the GT search (<= 16x16: one wave; larger: four), small batches one launch with 8 waves for every PU.
 #include "hop_dev.h"
 
 __constant__ int16_t c_luma_taps[4][8] = {
@@ -17,7 +19,9 @@ __constant__ int8_t c_refine_h[9][2] = { {0,0},{0,-1},{0,1},{-1,0},{1,0},{-1,-1}
 __constant__ int8_t c_refine_q[9][2] = { {0,0},{0,-1},{0,1},{-1,-1},{1,-1},{-1,0},{1,0},{-1,1},{1,1} };   // TEncSearch.cpp:59-70
 
 // MAXD = largest PU side of the class: 16 (one wave per PU, no barriers: such a PU is a few hundred samples and the
-// fixed latencies of a 256-thread workgroup -- five barriers, 47 KB of LDS, 3 workgroups per CU -- dominated) or 64
+// fixed latencies of a 256-thread workgroup -- five barriers, 47 KB of LDS, 3 workgroups per CU -- dominated; that holds while
+// the PUs outnumber the wave slots, i.e. for large batches: a request of a few dozen PUs leaves the device empty either way, and there
+// the five barriers cost less than the passes they save) or 64
 template <int MAXD>
 struct FracShared {
   static constexpr int TP = MAXD + 10;            // integer window pitch  (W+8 <= MAXD+8)
@@ -40,8 +44,8 @@ __global__ __launch_bounds__(NW * 64) void k_frac(const hop_pu_job* __restrict__
   typedef FracShared<MAXD> SH;
   constexpr int FR_TP = SH::TP, FR_PP = SH::PP, NT = NW * 64;
   __shared__ SH sh;
-  if (blockIdx.x >= *count) return;
-  const int pu = index[blockIdx.x];
+  if (index && blockIdx.x >= *count) return;
+  const int pu = index ? index[blockIdx.x] : (int)blockIdx.x;   // large batches: the PUs of the class (k_gt_prep); small batches: every PU of the request
   const hop_pu_job jb = jobs[pu];
   // only the fields the stage reads are loaded and only the ones it changes are stored: a local copy of the 100-byte result
   // lived on the scratch stack (40 B private segment per lane, 2.2 KB of HBM writes per PU, profiles/r01_traffic.json)
@@ -171,7 +175,17 @@ __global__ __launch_bounds__(NW * 64) void k_frac(const hop_pu_job* __restrict__
   }
 }
 
+constexpr int FRAC_WIDE_NW = 8;           // waves per PU of the small-batch form
+
 int hop_launch_frac(hop_ctx* c, int n, const hop_pu_job* d_jobs, hop_pu_result* d_res) {
+  if (hop_me_small_batch(n)) {            // one launch, a workgroup per PU, indexed directly (k_gt_search.hip: hop_me_small_batch)
+    const int pr = hop_prof_begin(c, HOP_K_FRAC, (uint64_t)n);
+    hipLaunchKernelGGL((k_frac<FRAC_WIDE_NW, 64>), dim3(n), dim3(FRAC_WIDE_NW * 64), 0, c->stream, d_jobs, hop_make_pics(c), d_res, (const int32_t*)nullptr, (const unsigned int*)nullptr);
+    hop_prof_end(c, pr);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hop_set_err(c, HOP_ERR_DEVICE, "frac launch: %s", hipGetErrorString(e));
+    return HOP_OK;
+  }
   // scratch (after the SS search's use of it on the same stream): 2 counters + 2 index lists, the layout of hop_launch_size_classes
   void* sc; int r = hop_scratch(c, 256 + (size_t)n * 8, &sc); if (r) return r;
   unsigned int* counts = (unsigned int*)sc;

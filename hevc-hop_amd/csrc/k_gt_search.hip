@@ -5,9 +5,14 @@
 // ProjectiveTransform GRID_SIZE-2 / bilinear branch (:904-1030) and xGetHADs / SAD cost.
 //
 // Mapping to CDNA4 (FP64-VALU bound: ~33 double-rate ops per warped sample, no HBM traffic beyond the patch)
-//   * PUs of up to 256 samples (16x16 and below) get ONE WAVE each (64-thread workgroups, no barriers at all:
-//     the search of such a PU is a chain of 6-18 short dependent iterations, so barrier and dispatch overhead, not
-//     arithmetic, decides); larger PUs get a 4-wave workgroup.  A prep kernel sorts the PUs into the two classes.
+//   * Two forms of the launch (hop_launch_gt, hop_me_small_batch).  LARGE batches (more than HOP_ME_WIDE_MAX PUs: the
+//     device is full, throughput per wave decides): PUs of up to 256 samples (16x16 and below) get ONE WAVE each
+//     (64-thread workgroups, no barriers at all: the search of such a PU is a chain of 6-18 short dependent
+//     iterations, so barrier and dispatch overhead, not arithmetic, decides); larger PUs get a 4-wave workgroup.  A
+//     prep kernel sorts the PUs into the two classes.  SMALL batches (the encode's requests: a few dozen PUs, most
+//     compute units idle, the kernel lasts as long as its slowest PU): one launch, every PU an 8-wave workgroup
+//     through the MAXD = 64 layout, indexed directly; the item loop of gt_eval deals the (candidate, block) items to
+//     however many waves there are, and nothing a PU computes depends on that number.
 //   * The 2Wx2H search patch (the reference's m_filteredBlock[0][0]: the SS reference around the start vector
 //     clamped to [0,maxVal]) sits in LDS as horizontally PAIRED samples (P[y][x], P[y][x+1]) so one LDS read
 //     feeds one bilinear row; the original block sits beside it.
@@ -270,7 +275,8 @@ __device__ static inline int gt_enumerate(SH& sh, const int (&cx)[4], const int 
   return sh.n_cand;
 }
 
-// NW = waves per PU (1 or 4); MAXD = largest PU side handled; the PUs of the class come through `index`
+// NW = waves per PU (1 or 4 for the size classes, 8 for small batches); MAXD = largest PU side handled; the PUs of the class come through `index`,
+// index == nullptr: workgroup b searches PU b (small batches).  Every wg_sync is reached by all waves of the workgroup: the control flow around them is uniform.
 template <typename PT, int NW, int MAXD>
 __global__ __launch_bounds__(NW * 64) void k_gt_search(const hop_pu_job* __restrict__ jobs, hop_pics pic, hop_pu_result* __restrict__ res,
                                                         const int32_t* __restrict__ index, const unsigned int* __restrict__ count) {
@@ -278,8 +284,9 @@ __global__ __launch_bounds__(NW * 64) void k_gt_search(const hop_pu_job* __restr
   __shared__ SH sh;
   constexpr int HS = 4 * (int)sizeof(PT);
   constexpr int NT = NW * 64;
-  if (blockIdx.x >= *count) return;
-  const int pu = index[blockIdx.x];
+  int pu;
+  if (index) { if (blockIdx.x >= *count) return; pu = index[blockIdx.x]; }       // large batches: the PUs of the class (k_gt_prep)
+  else { pu = blockIdx.x; if (res[pu].not_valid) return; }                       // small batches: every PU of the request, the ones k_gt_prep leaves out return here (uniform, before any barrier)
   const hop_pu_job* jp = jobs + pu;
   hop_pu_result* rp = res + pu;
   const int W = jp->w, H = jp->h, pu_x = jp->pu_x, pu_y = jp->pu_y, n_amvp = jp->n_amvp;
@@ -494,7 +501,31 @@ void hop_launch_size_classes(hop_ctx* c, int n, const hop_pu_job* d_jobs, const 
   hipLaunchKernelGGL(k_gt_prep, dim3((n + 255) / 256), dim3(256), 0, c->stream, d_jobs, d_res, n, counts, small_list, big_list);
 }
 
+// The two forms of a fractional / GT launch.  Up to HOP_ME_WIDE_MAX PUs (the encode's requests: a few dozen PUs with 256 compute units standing by, where a
+// kernel lasts as long as its slowest PU) every PU gets a workgroup of several waves in ONE launch, indexed directly; beyond it (the frozen-reference batches of
+// 10^5 PUs, where the device is full and throughput per wave decides) the PUs are sorted into the two size classes as before.  DESIGN.md 5 "Wide motion search" has
+// the measurements behind the value.  Developer switch HOP_ME_WIDE (read per call: the tests flip it; the results do not depend on it): 0 = always the size
+// classes, 2 = always the small-batch form, unset or 1 = by the threshold.
+constexpr int HOP_ME_WIDE_MAX = 512;
+bool hop_me_small_batch(int n) {
+  const char* e = getenv("HOP_ME_WIDE");
+  const int v = e ? atoi(e) : 1;
+  return v == 2 || (v != 0 && n <= HOP_ME_WIDE_MAX);
+}
+
+constexpr int GT_WIDE_NW = 8;             // waves per PU of the small-batch form, every PU through the MAXD = 64 layout (the patch pitch follows W at run time)
+
 int hop_launch_gt(hop_ctx* c, int n, const hop_pu_job* d_jobs, hop_pu_result* d_res) {
+  if (hop_me_small_batch(n)) {            // one launch, a workgroup per PU: no class lists, no counters; the largest and the smallest PU of the request run side by side
+    hop_pics pic = hop_make_pics(c);
+    const int pr = hop_prof_begin(c, HOP_K_GT_SEARCH, (uint64_t)n);
+    if (c->bd_y == 8) hipLaunchKernelGGL((k_gt_search<uint16_t, GT_WIDE_NW, 64>), dim3(n), dim3(GT_WIDE_NW * 64), 0, c->stream, d_jobs, pic, d_res, (const int32_t*)nullptr, (const unsigned int*)nullptr);
+    else              hipLaunchKernelGGL((k_gt_search<uint32_t, GT_WIDE_NW, 64>), dim3(n), dim3(GT_WIDE_NW * 64), 0, c->stream, d_jobs, pic, d_res, (const int32_t*)nullptr, (const unsigned int*)nullptr);
+    hop_prof_end(c, pr);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hop_set_err(c, HOP_ERR_DEVICE, "gt_search launch: %s", hipGetErrorString(e));
+    return HOP_OK;
+  }
   // scratch (after the SS search's use of it on the same stream): 2 counters + 2 index lists
   void* sc; int r = hop_scratch(c, 256 + (size_t)n * 8, &sc); if (r) return r;
   unsigned int* counts = (unsigned int*)sc;
