@@ -26,6 +26,8 @@ extern "C" {
 int hop_ent_init_states(uint8_t st[EN_STATES], int slice_type, int qp);                                            // host/hop_entropy.cpp
 int hop_parse_check(int pic_w, int pic_h, int bit_depth, int n_pic, const hop_slice_data_params* p, const uint8_t* data, const uint32_t* substream_bytes, int n_substreams,
                     const hop_cu_part* parts, const hop_sao_param* sao, size_t* total, char* err, size_t errn);     // host/hop_parse.cpp
+__attribute__((visibility("hidden"))) int hop_parse_device(hop_ctx* c, const hop_slice_data_params* p, const uint8_t* data, const uint8_t* d_data, const uint32_t* substream_bytes,
+                                                           int32_t n_substreams, hop_cu_part* parts, int32_t* levels, hop_sao_param* sao, size_t front);
 }
 
 namespace {
@@ -88,14 +90,41 @@ __global__ __launch_bounds__(64) void k_parse_diag(ParArgs A, int d, int r0, int
 }
 }  // namespace
 
+// the work area: the outputs, the models, the substreams' places and states, and (when the data comes from the host) the data
+struct ParLayout { size_t o_parts, o_levels, o_sao, o_init, o_entry, o_offs, o_sizes, o_state, o_data, end; };
+static ParLayout par_layout(size_t front, int n_pic, int n, int hctu, int n_blocks, bool with_levels, bool with_sao, size_t own_data) {
+  ParLayout L;
+  size_t end = front;
+  auto seg = [&](size_t bytes) { const size_t at = (end + 255) & ~(size_t)255; end = at + bytes; return at; };
+  L.o_parts = seg(sizeof(hop_cu_part) * 256 * (size_t)n * n_pic); L.o_levels = seg(with_levels ? sizeof(int32_t) * 6144 * (size_t)n * n_pic : 0);
+  L.o_sao = seg(with_sao ? sizeof(hop_sao_param) * 3 * (size_t)n * n_pic : 0); L.o_init = seg(EN_STATES); L.o_entry = seg((size_t)n_pic * hctu * EN_STATES);
+  L.o_offs = seg(sizeof(unsigned long long) * n_blocks); L.o_sizes = seg(sizeof(uint32_t) * n_blocks); L.o_state = seg(sizeof(ParState) * n_blocks); L.o_data = seg(own_data);
+  L.end = end;
+  return L;
+}
+
+// internal: an upper bound of what hop_parse_device adds to the scratch area behind `front` bytes of its caller's, for a context of one picture
+extern "C" __attribute__((visibility("hidden"))) size_t hop_parse_work_bytes(const hop_ctx* c, size_t data_bytes, int n_substreams) {
+  const int wctu = (c->pic_w + 63) / 64, hctu = (c->pic_h + 63) / 64;
+  return par_layout(0, 1, wctu * hctu, hctu, n_substreams, true, true, data_bytes + 256).end + 256;
+}
+
 extern "C" int hop_slice_data_parse(hop_ctx* c, const hop_slice_data_params* p, const uint8_t* data, const uint32_t* substream_bytes, int32_t n_substreams,
                                     hop_cu_part* parts, int32_t* levels, hop_sao_param* sao) {
   if (!c || !p || !data || !substream_bytes || !parts) return hop_set_err(c, HOP_ERR_ARG, "hop_slice_data_parse: bad argument");
+  return hop_parse_device(c, p, data, nullptr, substream_bytes, n_substreams, parts, levels, sao, 0);
+}
+
+// internal: the parser over substreams that are on the host (data) or already on the device (d_data, inside the first `front` bytes of the context's scratch area, which
+// the caller sized with hop_parse_work_bytes so that it does not move here): hop_access_unit_decode hands over what its compact kernel wrote
+extern "C" __attribute__((visibility("hidden"))) int hop_parse_device(hop_ctx* c, const hop_slice_data_params* p, const uint8_t* data, const uint8_t* d_data, const uint32_t* substream_bytes, int32_t n_substreams,
+                                hop_cu_part* parts, int32_t* levels, hop_sao_param* sao, size_t front) {
+  if (!c || !p || (!data && !d_data) || !substream_bytes || !parts) return hop_set_err(c, HOP_ERR_ARG, "hop_slice_data_parse: bad argument");
   if (c->shard_world > 1) return hop_set_err(c, HOP_ERR_ARG, "hop_slice_data_parse: a sharded context parses no slice data");
   if (c->bd_y != c->bd_c) return hop_set_err(c, HOP_ERR_ARG, "hop_slice_data_parse: luma and chroma bit depths differ");
   const int n_pic = c->sub_pitch ? (c->pic_h - c->sub_h) / c->sub_pitch + 1 : 1, ph = c->sub_pitch ? c->sub_h : c->pic_h;
   char err[256]; size_t total = 0;
-  int r = hop_parse_check(c->pic_w, ph, c->bd_y, n_pic, p, data, substream_bytes, n_substreams, parts, sao, &total, err, sizeof(err));
+  int r = hop_parse_check(c->pic_w, ph, c->bd_y, n_pic, p, data ? data : d_data, substream_bytes, n_substreams, parts, sao, &total, err, sizeof(err));
   if (r) return hop_set_err(c, r, "%s", err);
   uint8_t init[EN_STATES];
   if (hop_ent_init_states(init, p->slice_type, p->qp)) return hop_set_err(c, HOP_ERR_ARG, "hop_slice_data_parse: slice type %d", p->slice_type);
@@ -105,14 +134,14 @@ extern "C" int hop_slice_data_parse(hop_ctx* c, const hop_slice_data_params* p, 
   { unsigned long long at = 0; for (int i = 0; i < n_blocks; i++) { offs[i] = at; at += substream_bytes[i]; } }
   const size_t units = (size_t)n * n_pic * 256, parts_bytes = sizeof(hop_cu_part) * units, level_bytes = levels ? sizeof(int32_t) * 6144 * (size_t)n * n_pic : 0,
                sao_bytes = sao ? sizeof(hop_sao_param) * 3 * (size_t)n * n_pic : 0;
-  size_t end = 0;
-  auto seg = [&](size_t bytes) { const size_t at = (end + 255) & ~(size_t)255; end = at + bytes; return at; };
-  const size_t o_parts = seg(parts_bytes), o_levels = seg(level_bytes), o_sao = seg(sao_bytes), o_init = seg(EN_STATES), o_entry = seg((size_t)n_pic * hctu * EN_STATES),
-               o_offs = seg(sizeof(unsigned long long) * n_blocks), o_sizes = seg(sizeof(uint32_t) * n_blocks), o_state = seg(sizeof(ParState) * n_blocks), o_data = seg(total + 256);
-  void* buf; r = hop_scratch(c, end, &buf); if (r) return r;
+  const ParLayout L = par_layout(front, n_pic, n, hctu, n_blocks, levels != nullptr, sao != nullptr, d_data ? 0 : total + 256);
+  const size_t o_parts = L.o_parts, o_levels = L.o_levels, o_sao = L.o_sao, o_init = L.o_init, o_entry = L.o_entry, o_offs = L.o_offs, o_sizes = L.o_sizes, o_state = L.o_state,
+               o_data = L.o_data;
+  if (d_data && (!c->scratch || L.end > c->scratch_bytes)) return hop_set_err(c, HOP_ERR_STATE, "hop_slice_data_parse: the caller's scratch area of %zu bytes does not hold %zu", c->scratch_bytes, L.end);
+  void* buf; r = hop_scratch(c, L.end, &buf); if (r) return r;
   char* b = (char*)buf;
   HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipMemcpyAsync(b + o_data, data, total, hipMemcpyHostToDevice, c->stream));
+  if (!d_data) HIPCHK(c, hipMemcpyAsync(b + o_data, data, total, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(b + o_init, init, EN_STATES, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(b + o_offs, offs.data(), sizeof(unsigned long long) * n_blocks, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(b + o_sizes, substream_bytes, sizeof(uint32_t) * n_blocks, hipMemcpyHostToDevice, c->stream));
@@ -128,7 +157,7 @@ extern "C" int hop_slice_data_parse(hop_ctx* c, const hop_slice_data_params* p, 
   A.pic.wpp = p->wpp; A.pic.sao_shift = c->bd_y - std::min(c->bd_y, 10); A.pic.mi_size = p->mi_size; A.pic.mi_merge = !p->plain_intra;
   A.n_pic = n_pic; A.n_sub = n_sub;
   A.init = (const uint8_t*)(b + o_init); A.entry = (uint8_t*)(b + o_entry);
-  A.data = (const uint8_t*)(b + o_data); A.offs = (const unsigned long long*)(b + o_offs); A.sizes = (const uint32_t*)(b + o_sizes);
+  A.data = d_data ? d_data : (const uint8_t*)(b + o_data); A.offs = (const unsigned long long*)(b + o_offs); A.sizes = (const uint32_t*)(b + o_sizes);
   A.state = (ParState*)(b + o_state);
   hipLaunchKernelGGL(k_parse_init, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, c->stream, A.pic.parts, units);
   if (!p->wpp) {

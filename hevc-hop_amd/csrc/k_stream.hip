@@ -19,6 +19,8 @@
 // The input of a job is a virtual concatenation -- `head` (the uploaded NAL and slice header), then `body` (the substreams where k_entropy_pack left them): no copy.
 // Jobs (pictures of a stack) are the grid's y dimension.  An all-zero buffer costs what random bytes cost: no lane looks back further than its chunk.
 // No kernel looks at another workgroup's progress.
+// The way back -- hop_rbsp_unescape, hop_access_unit_read, hop_access_unit_decode -- is further down: k_une_count / k_une_scan / k_une_compact remove emulation
+// prevention (the syntax is host/hop_stream_read.cpp), and the decode entry hands the compact kernel's output to the parser's kernels (csrc/k_parse.hip).
 #include <string.h>
 #include <algorithm>
 #include <vector>
@@ -34,7 +36,11 @@ void hop_strm_parameter_sets(int pic_w, int pic_h, int bit_depth, const hop_stre
 void hop_strm_slice_header(int pic_w, int pic_h, const hop_stream_params* p, const uint32_t* sub_bytes, const uint32_t* sub_emul, int n_sub, std::vector<uint8_t>& s);
 void hop_strm_sei(int method, const uint8_t digest[3][16], std::vector<uint8_t>& s);
 void hop_strm_hash_plane(int method, int bit_depth, const int16_t* plane, int w, int h, size_t stride, uint8_t digest[16]);
+size_t hop_parse_work_bytes(const hop_ctx* c, size_t data_bytes, int n_substreams);                                                                         // k_parse.hip
+int hop_parse_device(hop_ctx* c, const hop_slice_data_params* p, const uint8_t* data, const uint8_t* d_data, const uint32_t* substream_bytes, int32_t n_substreams,
+                     hop_cu_part* parts, int32_t* levels, hop_sao_param* sao, size_t front);
 }
+#include "../host/hop_stream_read.h"
 
 namespace {
 constexpr int ESC_LANE = 16, ESC_THREADS = 256, ESC_CHUNK = ESC_LANE * ESC_THREADS;
@@ -246,6 +252,124 @@ __global__ __launch_bounds__(ESC_THREADS) void k_esc_scatter(const EscJob* __res
     if (at < J.out_cap) J.out[at] = v[j];
     at++;
     if (chunk + rel0 + j == J.total - 1 && v[j] == 0) { if (at < J.out_cap) J.out[at] = 3; }   // the final 03
+  }
+}
+
+// ---- the other direction: emulation prevention removed (convertPayloadToRBSP, TLibDecoder/NALread.cpp:52-77) ----
+// Byte i of the input is dropped exactly when it is 03 and the two bytes in front of it are 00 00: the sequential rule's counter is reset by the byte it drops, but that
+// byte is not zero, so the counter at i is the number of zeros immediately in front of i in the INPUT and the predicate is local -- two bytes back, and one ahead for the
+// second kind of violation.  No carry class, no max-scan:
+//   k_une_count    per chunk the dropped bytes (and, per segment, into the segment's word by atomicAdd: TDecCAVLC.cpp:1343-1353), the violations
+//   k_une_scan     one block per job: the dropped bytes in front of every chunk, the output's length
+//   k_une_compact  the flags again, an exclusive prefix over the lanes, the kept bytes stored below the capacity only
+struct UneJob {
+  const uint8_t* in; uint32_t lookback, total;               // in[0 .. lookback): what only the predicate sees; then the segments, `total` bytes; positions count from their start
+  const uint32_t* seg_end; uint32_t n_seg; uint32_t* seg_cnt;   // the segments' end positions (ascending, the last = total); per segment the bytes dropped inside it
+  uint32_t* chunk_cnt; uint32_t n_chunks;                    // count: dropped in the chunk; after the scan: dropped in front of it
+  uint8_t* out; unsigned long long out_cap; unsigned long long* out_total; uint32_t* violations;
+};
+__device__ static inline uint32_t une_segment_of(const UneJob& J, uint32_t pos) {
+  uint32_t lo = 0, hi = J.n_seg - 1;
+  while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (J.seg_end[mid] > pos) hi = mid; else lo = mid + 1; }
+  return lo;
+}
+// the lane's 16 bytes from position `at` with the two in front and the one behind: w[k] = the byte at at - 2 + k; ff in front of the lookback, 00 behind the end.
+// Returns the drop flags of the valid bytes; *viol: the violations among them.
+__device__ static inline uint32_t une_flags(const UneJob& J, uint32_t at, int n_valid, uint8_t w[ESC_LANE + 3], uint32_t* viol) {
+  const long long first = (long long)at - 2 + J.lookback;    // index into J.in of w[0]
+  if (first >= 0 && at + ESC_LANE + 1 <= J.total) __builtin_memcpy(w, J.in + first, ESC_LANE + 3);
+  else {
+#pragma unroll
+    for (int k = 0; k < ESC_LANE + 3; k++) { const long long i = first + k; w[k] = i < 0 ? 0xff : i < (long long)J.lookback + J.total ? J.in[i] : 0; }
+  }
+  uint32_t flags = 0, bad = 0;
+#pragma unroll
+  for (int j = 0; j < ESC_LANE; j++) {
+    if (j >= n_valid) continue;
+    const bool z2 = w[j] == 0 && w[j + 1] == 0;
+    const uint8_t b = w[j + 2];
+    const bool drop = z2 && b == 3;
+    flags |= (uint32_t)drop << j;
+    bad += (z2 && b <= 2) + (drop && w[j + 3] > 3);
+  }
+  if (viol) *viol = bad;
+  return flags;
+}
+
+__global__ __launch_bounds__(ESC_THREADS) void k_une_count(const UneJob* __restrict__ jobs) {
+  __shared__ uint32_t sums[4][2];
+  const UneJob J = jobs[blockIdx.y];
+  if (blockIdx.x >= J.n_chunks) return;                                  // (uniform: the whole block)
+  const uint32_t chunk = blockIdx.x * (uint32_t)ESC_CHUNK;
+  const int t = threadIdx.x;
+  const uint32_t at = chunk + (uint32_t)t * ESC_LANE;
+  const int n_valid = (int)min((uint32_t)ESC_LANE, J.total - min(J.total, at));
+  uint8_t w[ESC_LANE + 3];
+  uint32_t bad = 0;
+  const uint32_t flags = n_valid ? une_flags(J, at, n_valid, w, &bad) : 0u;
+  const uint32_t last = min(J.total, chunk + (uint32_t)ESC_CHUNK) - 1;
+  const uint32_t seg0 = une_segment_of(J, chunk);
+  const bool one_segment = J.seg_end[seg0] > last;
+  if (!one_segment && flags) {                                           // a chunk that holds a boundary: each dropped byte to the segment its position lies in
+    uint32_t seg = une_segment_of(J, at), acc = 0;
+#pragma unroll
+    for (int j = 0; j < ESC_LANE; j++) {
+      if (!((flags >> j) & 1u)) continue;
+      while (at + j >= J.seg_end[seg]) { if (acc) atomicAdd(&J.seg_cnt[seg], acc); acc = 0; seg++; }
+      acc++;
+    }
+    if (acc) atomicAdd(&J.seg_cnt[seg], acc);
+  }
+  uint32_t s2[2] = { (uint32_t)__popc(flags), bad };
+#pragma unroll
+  for (int k = 0; k < 2; k++) {
+    uint32_t x = s2[k];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+    if ((t & 63) == 0) sums[t >> 6][k] = x;
+  }
+  __syncthreads();
+  if (t == 0) {
+    const uint32_t cnt = sums[0][0] + sums[1][0] + sums[2][0] + sums[3][0], v = sums[0][1] + sums[1][1] + sums[2][1] + sums[3][1];
+    J.chunk_cnt[blockIdx.x] = cnt;
+    if (one_segment && cnt) atomicAdd(&J.seg_cnt[seg0], cnt);
+    if (v) atomicAdd(J.violations, v);
+  }
+}
+
+__global__ __launch_bounds__(ESC_THREADS) void k_une_scan(const UneJob* __restrict__ jobs) {
+  __shared__ uint32_t part[4];
+  const UneJob J = jobs[blockIdx.x];
+  const int t = threadIdx.x;
+  uint32_t run = 0;                                                      // dropped in front of the tile
+  for (uint32_t base = 0; base < J.n_chunks; base += ESC_THREADS) {
+    const uint32_t k = base + t;
+    const uint32_t cnt = k < J.n_chunks ? J.chunk_cnt[k] : 0u;
+    const uint32_t incl = esc_block_sum_scan(cnt, part);
+    if (k < J.n_chunks) J.chunk_cnt[k] = run + incl - cnt;
+    run += part[0] + part[1] + part[2] + part[3];
+    __syncthreads();                                                     // (part is written again by the next tile)
+  }
+  if (t == 0) *J.out_total = (unsigned long long)J.total - run;
+}
+
+__global__ __launch_bounds__(ESC_THREADS) void k_une_compact(const UneJob* __restrict__ jobs) {
+  __shared__ uint32_t part[4];
+  const UneJob J = jobs[blockIdx.y];
+  if (blockIdx.x >= J.n_chunks) return;
+  const uint32_t chunk = blockIdx.x * (uint32_t)ESC_CHUNK;
+  const uint32_t at = chunk + (uint32_t)threadIdx.x * ESC_LANE;
+  const int n_valid = (int)min((uint32_t)ESC_LANE, J.total - min(J.total, at));
+  uint8_t w[ESC_LANE + 3];
+  const uint32_t flags = n_valid ? une_flags(J, at, n_valid, w, nullptr) : 0u;
+  const uint32_t mine = __popc(flags);
+  const uint32_t before = esc_block_sum_scan(mine, part) - mine;
+  unsigned long long to = (unsigned long long)at - J.chunk_cnt[blockIdx.x] - before;
+#pragma unroll
+  for (int j = 0; j < ESC_LANE; j++) {
+    if (j >= n_valid || ((flags >> j) & 1u)) continue;
+    if (to < J.out_cap) J.out[to] = w[j + 2];
+    to++;
   }
 }
 
@@ -512,5 +636,164 @@ extern "C" int hop_access_unit_write(hop_ctx* c, const hop_stream_params* p, con
     au_bytes[k] = at - from;
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  return HOP_OK;
+}
+
+// ---- the stream read back ----
+namespace {
+// the work area of one unescape job behind `front` bytes of the caller's
+struct UneArea { size_t o_ends, o_cnt, o_chunks, o_job, o_total, o_viol, o_out, end; uint32_t n_chunks; size_t dev_cap; };
+UneArea une_area(size_t front, size_t total, int n_seg, size_t out_capacity) {
+  UneArea A;
+  size_t end = front;
+  auto seg = [&](size_t bytes) { const size_t at = align256(end); end = at + bytes; return at; };
+  A.n_chunks = chunks_of(total); A.dev_cap = std::min(out_capacity, total);
+  A.o_ends = seg(sizeof(uint32_t) * n_seg); A.o_cnt = seg(sizeof(uint32_t) * n_seg); A.o_chunks = seg(sizeof(uint32_t) * A.n_chunks); A.o_job = seg(sizeof(UneJob));
+  A.o_total = seg(sizeof(unsigned long long)); A.o_viol = seg(sizeof(uint32_t)); A.o_out = seg(A.dev_cap + ESC_LANE);
+  A.end = end;
+  return A;
+}
+// the three launches over d_in (lookback bytes, then the segments) enqueued, and what the host needs of their results brought back: the output's length, per segment
+// its RBSP bytes, the violations.  The RBSP stays at b + A.o_out.
+int une_run(hop_ctx* c, char* b, const UneArea& A, const uint8_t* d_in, int lookback, const uint32_t* segment_bytes, int n_seg, size_t total, unsigned long long* need,
+            uint32_t* rbsp_bytes, uint32_t* violations) {
+  std::vector<uint32_t> ends(n_seg);
+  { size_t at = 0; for (int i = 0; i < n_seg; i++) { at += segment_bytes[i]; ends[i] = (uint32_t)at; } }
+  UneJob J;
+  J.in = d_in; J.lookback = (uint32_t)lookback; J.total = (uint32_t)total;
+  J.seg_end = (const uint32_t*)(b + A.o_ends); J.n_seg = (uint32_t)n_seg; J.seg_cnt = (uint32_t*)(b + A.o_cnt);
+  J.chunk_cnt = (uint32_t*)(b + A.o_chunks); J.n_chunks = A.n_chunks;
+  J.out = (uint8_t*)(b + A.o_out); J.out_cap = A.dev_cap; J.out_total = (unsigned long long*)(b + A.o_total); J.violations = (uint32_t*)(b + A.o_viol);
+  HIPCHK(c, hipMemcpyAsync(b + A.o_ends, ends.data(), sizeof(uint32_t) * n_seg, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(b + A.o_cnt, 0, sizeof(uint32_t) * n_seg, c->stream));
+  HIPCHK(c, hipMemsetAsync(b + A.o_viol, 0, sizeof(uint32_t), c->stream));
+  HIPCHK(c, hipMemcpyAsync(b + A.o_job, &J, sizeof(J), hipMemcpyHostToDevice, c->stream));
+  const UneJob* dj = (const UneJob*)(b + A.o_job);
+  const int pr = hop_prof_begin(c, HOP_K_UNESCAPE, total);
+  hipLaunchKernelGGL(k_une_count, dim3(A.n_chunks, 1), dim3(ESC_THREADS), 0, c->stream, dj);
+  hipLaunchKernelGGL(k_une_scan, dim3(1), dim3(ESC_THREADS), 0, c->stream, dj);
+  hipLaunchKernelGGL(k_une_compact, dim3(A.n_chunks, 1), dim3(ESC_THREADS), 0, c->stream, dj);
+  hop_prof_end(c, pr);
+  HIPCHK(c, hipGetLastError());
+  std::vector<uint32_t> cnt(n_seg);
+  uint32_t viol = 0;
+  HIPCHK(c, hipMemcpyAsync(need, b + A.o_total, sizeof(*need), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(cnt.data(), b + A.o_cnt, sizeof(uint32_t) * n_seg, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&viol, b + A.o_viol, sizeof(viol), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  unsigned long long dropped = 0;
+  for (int i = 0; i < n_seg; i++) {
+    if (cnt[i] > segment_bytes[i]) return hop_set_err(c, HOP_ERR_DEVICE, "hop_rbsp_unescape: segment %d: %u of %u bytes dropped", i, cnt[i], segment_bytes[i]);
+    dropped += cnt[i];
+    if (rbsp_bytes) rbsp_bytes[i] = segment_bytes[i] - cnt[i];
+  }
+  if (*need + dropped != total) return hop_set_err(c, HOP_ERR_DEVICE, "hop_rbsp_unescape: %llu bytes kept and %llu dropped of %zu", *need, dropped, total);
+  if (violations) *violations = viol;
+  return HOP_OK;
+}
+
+// what hop_access_unit_read and hop_access_unit_decode share: the host pass over the syntax, the VCL unit's payload uploaded, the three launches.  Afterwards the
+// slice data's RBSP (*total bytes, sizes[] per substream) lies at *d_rbsp inside the first *front bytes of the scratch area, which was sized front + tail(front).
+template <typename Tail>
+int au_unescape(hop_ctx* c, const char* who, const uint8_t* au, size_t au_bytes, const hop_stream_info* active, int max_substreams, Tail tail, hop_strm_au& a,
+                std::vector<uint32_t>& sizes, size_t* total, const uint8_t** d_rbsp, size_t* front) {
+  if (c->shard_world > 1) return hop_set_err(c, HOP_ERR_ARG, "%s: a sharded context reads no stream", who);
+  if (c->sub_pitch || c->sub_h) return hop_set_err(c, HOP_ERR_ARG, "%s: a stacked context reads no stream (one picture per context)", who);
+  if (c->bd_y != c->bd_c) return hop_set_err(c, HOP_ERR_ARG, "%s: luma and chroma bit depths differ", who);
+  const int dims[3] = { c->pic_w, c->pic_h, c->bd_y };
+  char err[256];
+  int r = hop_strm_read_syntax(au, au_bytes, active, dims, max_substreams, &a, err, sizeof(err));
+  if (r) return hop_set_err(c, r, "%s", err);
+  const int n_sub = (int)a.seg.size(), back = std::min(2, (int)a.info.header_bytes);
+  const size_t payload = a.nal_len - (size_t)a.info.header_bytes;
+  const size_t o_in = 0, in_bytes = (size_t)back + payload;
+  const UneArea A = une_area(o_in + in_bytes + ESC_LANE, payload, n_sub, payload);
+  *front = align256(A.end);
+  void* buf; r = hop_scratch(c, *front + tail(*front), &buf); if (r) return r;
+  char* b = (char*)buf;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(b + o_in, au + a.nal_at + a.info.header_bytes - back, in_bytes, hipMemcpyHostToDevice, c->stream));
+  unsigned long long need = 0; uint32_t viol = 0;
+  sizes.assign(n_sub, 0);
+  r = une_run(c, b, A, (const uint8_t*)(b + o_in), back, a.seg.data(), n_sub, payload, &need, sizes.data(), &viol);
+  if (r) return r;
+  r = hop_strm_read_sizes(sizes.data(), n_sub, viol, err, sizeof(err));
+  if (r) return hop_set_err(c, r, "%s", err);
+  *total = (size_t)need; *d_rbsp = (const uint8_t*)(b + A.o_out);
+  return HOP_OK;
+}
+}  // namespace
+
+extern "C" int hop_rbsp_unescape(hop_ctx* c, const uint8_t* escaped, const uint32_t* segment_bytes, int32_t n_segments, int32_t lookback, uint8_t* out, size_t out_capacity,
+                                 size_t* out_bytes, uint32_t* segment_rbsp_bytes, uint32_t* violations) {
+  if (!c || !escaped || !segment_bytes || n_segments < 1 || lookback < 0 || lookback > 2 || !out_bytes || (!out && out_capacity))
+    return hop_set_err(c, HOP_ERR_ARG, "hop_rbsp_unescape: bad argument");
+  size_t total = 0;
+  for (int i = 0; i < n_segments; i++) {
+    if (!segment_bytes[i]) return hop_set_err(c, HOP_ERR_ARG, "hop_rbsp_unescape: segment %d is empty", i);
+    total += segment_bytes[i];
+    if (total > 0x7FFFFFFFu) return hop_set_err(c, HOP_ERR_ARG, "hop_rbsp_unescape: more than 2^31 - 1 bytes");
+  }
+  const size_t in_bytes = (size_t)lookback + total;
+  const UneArea A = une_area(in_bytes + ESC_LANE, total, n_segments, out_capacity);
+  void* buf; int r = hop_scratch(c, A.end, &buf); if (r) return r;
+  char* b = (char*)buf;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(b, escaped, in_bytes, hipMemcpyHostToDevice, c->stream));
+  unsigned long long need = 0;
+  r = une_run(c, b, A, (const uint8_t*)b, lookback, segment_bytes, n_segments, total, &need, segment_rbsp_bytes, violations);
+  if (r) return r;
+  *out_bytes = (size_t)need;
+  if (need > out_capacity) return hop_set_err(c, HOP_ERR_ARG, "hop_rbsp_unescape: the RBSP takes %llu bytes, out_capacity is %zu", need, out_capacity);
+  if (need) HIPCHK(c, hipMemcpy(out, b + A.o_out, (size_t)need, hipMemcpyDeviceToHost));
+  return HOP_OK;
+}
+
+extern "C" int hop_access_unit_read(hop_ctx* c, const uint8_t* au, size_t au_bytes, const hop_stream_info* active, hop_stream_info* info, uint8_t* data, size_t data_capacity,
+                                    size_t* data_bytes, uint32_t* substream_bytes, int32_t max_substreams, uint8_t (*digest)[16]) {
+  if (!c || !au || !info || !data_bytes || !substream_bytes || !digest || (!data && data_capacity)) return hop_set_err(c, HOP_ERR_ARG, "hop_access_unit_read: bad argument");
+  hop_strm_au a; std::vector<uint32_t> sizes; size_t total = 0, front = 0; const uint8_t* d_rbsp = nullptr;
+  int r = au_unescape(c, "hop_access_unit_read", au, au_bytes, active, max_substreams, [](size_t) { return (size_t)0; }, a, sizes, &total, &d_rbsp, &front);
+  if (r) return r;
+  memcpy(substream_bytes, sizes.data(), sizeof(uint32_t) * sizes.size());
+  *data_bytes = total; *info = a.info;
+  memcpy(digest, a.digest, sizeof(a.digest));
+  if (total > data_capacity) return hop_set_err(c, HOP_ERR_ARG, "hop_access_unit_read: the slice data takes %zu bytes, data_capacity is %zu", total, data_capacity);
+  HIPCHK(c, hipMemcpy(data, d_rbsp, total, hipMemcpyDeviceToHost));
+  return HOP_OK;
+}
+
+extern "C" int hop_access_unit_decode(hop_ctx* c, const uint8_t* au, size_t au_bytes, const hop_stream_info* active, hop_stream_info* info, int32_t hash_match[3],
+                                      hop_cu_part* parts, int32_t* levels, hop_sao_param* sao_coded) {
+  if (!c || !au || !info || !hash_match) return hop_set_err(c, HOP_ERR_ARG, "hop_access_unit_decode: bad argument");
+  const int wctu = (c->pic_w + 63) / 64, hctu = (c->pic_h + 63) / 64, n_ctu = wctu * hctu;
+  hop_strm_au a; std::vector<uint32_t> sizes; size_t total = 0, front = 0; const uint8_t* d_rbsp = nullptr;
+  // the parser's work area goes behind the unescape's in one allocation, so that the RBSP stays where the compact kernel put it
+  int r = au_unescape(c, "hop_access_unit_decode", au, au_bytes, active, hctu, [&](size_t) { return hop_parse_work_bytes(c, 0, hctu); }, a, sizes, &total, &d_rbsp, &front);
+  if (r) return r;
+  const hop_slice_data_params& sl = a.info.params.slice;
+  const bool sao_on = sl.sao_luma || sl.sao_chroma;
+  std::vector<hop_cu_part> own_parts; std::vector<int32_t> own_levels; std::vector<hop_sao_param> own_sao;
+  if (!parts) { own_parts.resize((size_t)n_ctu * 256); parts = own_parts.data(); }
+  if (!levels) { own_levels.resize((size_t)n_ctu * 6144); levels = own_levels.data(); }
+  if (sao_on && !sao_coded) { own_sao.resize((size_t)n_ctu * 3); sao_coded = own_sao.data(); }
+  r = hop_parse_device(c, &sl, nullptr, d_rbsp, sizes.data(), (int32_t)sizes.size(), parts, levels, sao_on ? sao_coded : nullptr, front);
+  if (r) return r;
+  hop_dec_params dp; dp.qp = sl.qp; dp.cb_qp_offset = 0; dp.cr_qp_offset = 0; dp.plain_intra = sl.plain_intra; dp.schedule = 0;
+  r = hop_decode_frame(c, &dp, parts, levels); if (r) return r;
+  hop_deblock_params db; db.qp = sl.qp; db.beta_offset_div2 = 0; db.tc_offset_div2 = 0; db.cb_qp_offset = 0; db.cr_qp_offset = 0; db.disable = 0;
+  r = hop_deblock_frame(c, &db, parts); if (r) return r;
+  if (sao_on) {
+    std::vector<hop_sao_param> recon((size_t)n_ctu * 3);
+    if (hop_sao_reconstruct_params(n_ctu, wctu, c->bd_y, sao_coded, recon.data())) return hop_set_err(c, HOP_ERR_ARG, "hop_access_unit_decode: the coded SAO parameters name a merge candidate that is not there");
+    r = hop_sao_apply(c, recon.data()); if (r) return r;
+  }
+  hash_match[0] = hash_match[1] = hash_match[2] = -1;
+  if (a.info.params.hash == 1 || a.info.params.hash == 3) {
+    uint8_t got[3][16];
+    r = hop_picture_hash(c, a.info.params.hash, got); if (r) return r;
+    for (int k = 0; k < 3; k++) hash_match[k] = !memcmp(got[k], a.digest[k], 16);
+  }
+  *info = a.info;
   return HOP_OK;
 }

@@ -125,6 +125,7 @@ class DecParams(ctypes.Structure):       # hop_dec_params
 HOP_K_ENTROPY_CTX, HOP_K_ENTROPY = 21, 22          # hop_profile_read ids of hop_slice_data_write's context pass and coding pass
 HOP_K_PARSE = 23                                   # ... and of hop_slice_data_parse's launches
 HOP_K_ESCAPE, HOP_K_PICHASH = 24, 25               # ... of the emulation-prevention launches and the checksum pass (hop_access_unit_write, hop_rbsp_escape, hop_picture_hash)
+HOP_K_UNESCAPE = 26                                # ... of the count, scan and compact launches that remove emulation prevention (hop_rbsp_unescape, hop_access_unit_read / _decode)
 
 
 PARSE_GUARD = 256   # bytes behind each output of the slice-data parser that must come back untouched
@@ -160,6 +161,11 @@ class StreamParams(ctypes.Structure):   # hop_stream_params
     _fields_ = [("slice", SliceDataParams), ("poc", ctypes.c_int32), ("parameter_sets", ctypes.c_int32), ("hash", ctypes.c_int32)]
 
 
+class StreamInfo(ctypes.Structure):   # hop_stream_info
+    _fields_ = [("pic_w", ctypes.c_int32), ("pic_h", ctypes.c_int32), ("bit_depth", ctypes.c_int32), ("params", StreamParams), ("nal_type", ctypes.c_int32),
+                ("n_substreams", ctypes.c_int32), ("header_bytes", ctypes.c_int32)]
+
+
 _I16P = ctypes.POINTER(ctypes.c_int16)
 
 
@@ -174,7 +180,7 @@ MIRRORS = {"hop_pu_job": PU_JOB_DTYPE, "hop_pu_result": PU_RESULT_DTYPE, "hop_pr
            "hop_rqt_result": RQT_RESULT_DTYPE, "hop_cu_syntax": CU_SYNTAX_DTYPE, "hop_intra_cu_syntax": INTRA_CU_SYNTAX_DTYPE, "hop_intra_rqt_opt": INTRA_RQT_OPT_DTYPE,
            "hop_intra_search_job": INTRA_SEARCH_JOB_DTYPE, "hop_intra_search_result": INTRA_SEARCH_RESULT_DTYPE, "hop_cu_part": CU_PART_DTYPE, "hop_enc_params": EncParams,
            "hop_deblock_params": DeblockParams, "hop_sao_param": SAO_PARAM_DTYPE, "hop_sao_params": SaoParams, "hop_dec_params": DecParams,
-           "hop_slice_data_params": SliceDataParams, "hop_stream_params": StreamParams}
+           "hop_slice_data_params": SliceDataParams, "hop_stream_params": StreamParams, "hop_stream_info": StreamInfo}
 
 
 def mirror_size(m):
@@ -517,6 +523,39 @@ class Context:
         counts of the segments alone or None).  An output that does not fit raises HopError with .needed."""
         return _rbsp_escape(self.L, self.L.hop_rbsp_escape, self.h, data, segments, capacity, guard, want_counts)
 
+    def rbsp_unescape(self, data, segments=None, lookback=0, capacity=None, guard=0):
+        """hop_rbsp_unescape: emulation prevention removed on the device -- data: `lookback` bytes only the predicate sees, then the segments (escaped byte lengths; default:
+        one).  Returns (RBSP bytes, per segment its RBSP bytes, violations).  An output that does not fit raises HopError with .needed."""
+        return _rbsp_unescape(self.L, self.L.hop_rbsp_unescape, self.h, data, segments, lookback, capacity, guard)
+
+    def access_unit_read(self, au, active=None, max_substreams=None, capacity=None):
+        """hop_access_unit_read: one access unit's Annex B bytes -> (StreamInfo, the slice data's RBSP as slice_data_parse takes it, the substreams' sizes, the SEI's digests
+        (3, 16) uint8); active: the StreamInfo of an earlier access unit of the sequence.  HopError with .code (and .needed when the RBSP does not fit capacity)."""
+        return _access_unit_read(self.L, self.L.hop_access_unit_read, self.h, au, active, max_substreams, capacity)
+
+    def access_unit_decode(self, au, active=None, want_outputs=True):
+        """hop_access_unit_decode: one access unit's bytes to the picture resident in the context (recon_download).  Returns (StreamInfo, hash_match [3]: 1 equal, 0
+        different, -1 not checked, parts, levels, coded SAO parameters or None); want_outputs False: the three are not asked for (None)."""
+        au = np.frombuffer(bytes(au), np.uint8).copy() if len(au) else np.zeros(1, np.uint8)
+        n = self._n_ctu()
+        info = StreamInfo(); match = (ctypes.c_int32 * 3)(-2, -2, -2)
+        out = [np.full(nb + PARSE_GUARD, 0xA5, np.uint8) if want_outputs else None for nb in (n * 256 * CU_PART_DTYPE.itemsize, n * 6144 * 4, n * 3 * SAO_PARAM_DTYPE.itemsize)]
+        self.L.hop_access_unit_decode.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_void_p] * 6
+        r = self.L.hop_access_unit_decode(self.h, au.ctypes.data, len(au), None if active is None else ctypes.byref(active), ctypes.byref(info), match,
+                                          *[None if b is None else b.ctypes.data for b in out])
+        for b in out:
+            assert b is None or np.all(b[-PARSE_GUARD:] == 0xA5), "hop_access_unit_decode stored past an output"
+        if r != 0:
+            e = HopError("hop_access_unit_decode: %d %s" % (r, self.L.hop_last_error(self.h).decode()))
+            e.code = r
+            raise e
+        if not want_outputs:
+            return info, list(match), None, None, None
+        parts, levels, sao = _parse_out(n, out, "hop_access_unit_decode")
+        if not (info.params.slice.sao_luma or info.params.slice.sao_chroma):
+            sao = None
+        return info, list(match), parts, levels, sao
+
     def picture_hash(self, method):
         """hop_picture_hash: the decoded-picture hash of the resident reconstruction, (pictures, 3, 16) uint8 -- method 1 MD5, 3 checksum (4 bytes, then zeros)"""
         d = np.zeros((self.pictures, 3, 16), np.uint8)
@@ -833,6 +872,76 @@ def rbsp_escape_host(data, segments=None, capacity=None, guard=0, want_counts=Tr
     """hop_rbsp_escape_host: the sequential rule on the host (the yardstick of Context.rbsp_escape); same results and HopError"""
     L = lib or load()
     return _rbsp_escape(L, L.hop_rbsp_escape_host, None, data, segments, capacity, guard, want_counts)
+
+
+def _rbsp_unescape(L, fn, ctx, data, segments, lookback, capacity, guard):
+    data = bytes(data)
+    a = np.frombuffer(data, np.uint8).copy() if data else np.zeros(1, np.uint8)
+    seg = np.asarray([len(data) - lookback] if segments is None else segments, np.uint32)
+    assert int(seg.astype(np.uint64).sum()) + lookback == len(data), "lookback and the segment sizes do not add up to the data"
+    cap = len(data) if capacity is None else capacity
+    buf = np.full(cap + guard, 0xA5, np.uint8); n = ctypes.c_size_t(0); cnt = np.zeros(max(1, len(seg)), np.uint32); viol = ctypes.c_uint32(0)
+    tail = [a.ctypes.data, seg.ctypes.data, len(seg), lookback, buf.ctypes.data, cap, ctypes.byref(n), cnt.ctypes.data, ctypes.byref(viol)]
+    fn.argtypes = ([ctypes.c_void_p] if ctx is not None else []) + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_void_p] * 3
+    r = fn(*(([ctx] if ctx is not None else []) + tail))
+    assert np.all(buf[cap:] == 0xA5), "hop_rbsp_unescape stored past out_capacity"
+    if r != 0:
+        e = HopError("hop_rbsp_unescape: %d %s" % (r, L.hop_last_error(ctx).decode() if ctx is not None else ""))
+        e.code = r; e.needed = n.value
+        raise e
+    return buf[:n.value].tobytes(), cnt[:len(seg)], int(viol.value)
+
+
+def rbsp_unescape_host(data, segments=None, lookback=0, capacity=None, guard=0, lib=None):
+    """hop_rbsp_unescape_host: the sequential rule on the host (the yardstick of Context.rbsp_unescape); same results and HopError"""
+    L = lib or load()
+    return _rbsp_unescape(L, L.hop_rbsp_unescape_host, None, data, segments, lookback, capacity, guard)
+
+
+READ_GUARD = 64   # bytes of 0xA5 behind every output of the access-unit readers that must come back untouched
+
+
+def _access_unit_read(L, fn, ctx, au, active, max_substreams, capacity):
+    au = bytes(au)
+    a = np.frombuffer(au, np.uint8).copy() if au else np.zeros(1, np.uint8)
+    cap = len(au) if capacity is None else capacity
+    nmax = 1024 if max_substreams is None else max_substreams
+    G = READ_GUARD
+    info = np.full(ctypes.sizeof(StreamInfo) + G, 0xA5, np.uint8); data = np.full(cap + G, 0xA5, np.uint8)
+    sizes = np.full(4 * max(nmax, 0) + G, 0xA5, np.uint8); digest = np.full(48 + G, 0xA5, np.uint8); n = ctypes.c_size_t(0)
+    fn.argtypes = ([ctypes.c_void_p] if ctx is not None else []) + [ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_void_p] * 3 + [ctypes.c_size_t] + [ctypes.c_void_p] * 2 + [ctypes.c_int32, ctypes.c_void_p]
+    r = fn(*(([ctx] if ctx is not None else []) + [a.ctypes.data, len(au), None if active is None else ctypes.byref(active), info.ctypes.data, data.ctypes.data, cap,
+                                                    ctypes.byref(n), sizes.ctypes.data, nmax, digest.ctypes.data]))
+    for b in (info, data, sizes, digest):
+        assert np.all(b[-G:] == 0xA5), "hop_access_unit_read stored past an output"
+    if r != 0:
+        e = HopError("hop_access_unit_read: %d %s" % (r, L.hop_last_error(ctx).decode() if ctx is not None else ""))
+        e.code = r; e.needed = n.value
+        raise e
+    si = StreamInfo.from_buffer_copy(info[:ctypes.sizeof(StreamInfo)].tobytes())
+    return si, data[:n.value].tobytes(), sizes[:4 * si.n_substreams].view(np.uint32).copy(), digest[:48].reshape(3, 16).copy()
+
+
+def access_unit_read_host(au, active=None, max_substreams=None, capacity=None, lib=None):
+    """hop_access_unit_read_host: the host build of the stream reader (the yardstick of Context.access_unit_read), no device; same results and HopError"""
+    L = lib or load()
+    return _access_unit_read(L, L.hop_access_unit_read_host, None, au, active, max_substreams, capacity)
+
+
+def annexb_access_units(stream, lib=None):
+    """hop_annexb_access_unit, repeated: the access units of an Annex B stream as a list of bytes"""
+    L = lib or load()
+    stream = bytes(stream)
+    a = np.frombuffer(stream, np.uint8).copy() if stream else np.zeros(1, np.uint8)
+    L.hop_annexb_access_unit.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    out, at = [], 0
+    while at < len(stream):
+        n = ctypes.c_size_t(0)
+        r = L.hop_annexb_access_unit(a.ctypes.data + at, len(stream) - at, ctypes.byref(n))
+        if r != 0 or n.value == 0:
+            raise HopError("hop_annexb_access_unit: %d at byte %d" % (r, at))
+        out.append(stream[at:at + n.value]); at += n.value
+    return out
 
 
 def parameter_sets_write(W, H, bit_depth=8, qp=32, slice_type=3, wpp=0, plain_intra=0, sao=1, mi_size=16, lib=None):

@@ -335,6 +335,7 @@ int hop_sizeof(const char* name) {
   S(hop_dec_params);
   S(hop_slice_data_params);
   S(hop_stream_params);
+  S(hop_stream_info);
 #undef S
   return -1;
 }

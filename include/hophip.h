@@ -825,7 +825,7 @@ int hop_slice_data_write_host(int pic_w, int pic_h, int bit_depth, const hop_sli
  * n_substreams: per picture, the CTU rows with wpp, 1 without.  A stacked context parses its pictures one after the other in data, substream_bytes and the outputs.
  * Outputs, in the layouts hop_decode_frame, hop_deblock_frame, hop_sao_reconstruct_params and hop_slice_data_write take: parts 256 per CTU, levels 6144 per CTU (may be
  * NULL: parsed and dropped), sao_coded 3 per CTU (non-NULL iff an SAO flag is set).  Not parsed here: parameter sets, the slice header and its entry points, SEI, NAL
- * framing, emulation prevention -- the caller's.  Call sequence of a decode: hop_slice_data_parse -> hop_decode_frame -> hop_deblock_frame ->
+ * framing, emulation prevention -- hop_access_unit_read (below) reads them and hands this entry its input; hop_access_unit_decode runs the whole chain.  Call sequence of a decode: hop_slice_data_parse -> hop_decode_frame -> hop_deblock_frame ->
  * hop_sao_reconstruct_params -> hop_sao_apply.
  * What the stream does not carry, and what the parser stores there (hop_encode_frame's values, so that parts parsed from a stream it wrote compare equal):
  *   a unit outside the picture (partial CTU), or never reached because its substream stopped: pred_mode 15, part_size 15, ref_idx -1, mvp_idx -1, mvp_num -1,
@@ -907,6 +907,69 @@ int hop_rbsp_escape_host(const uint8_t* rbsp, const uint32_t* segment_bytes, int
  * the host -- MD5 is one dependent chain per plane; method 3 (checksum) is a device pass.  Above 8 bit a sample is hashed as two bytes, low byte first. */
 int hop_picture_hash(hop_ctx* ctx, int method, uint8_t (*digest)[16]);
 
+/* ---- the stream read back: a picture's access unit (Annex B) into slice data, and into a picture ---- */
+/* replaces: the removal of emulation prevention in convertPayloadToRBSP (TLibDecoder/NALread.cpp:52-77) with the bookkeeping parseSliceHeader does on its result
+ * (TLibDecoder/TDecCAVLC.cpp:1343-1353: every entry point less the emulation-prevention bytes whose position in the NAL unit lies inside it), on the device.
+ * escaped: `lookback` (0..2) bytes that only the predicate sees -- the last bytes in front of the first segment, a slice header's; they are not output --, then n_segments
+ * segments of ESCAPED bytes back to back, segment_bytes[i] each, counted in the escaped domain as the entry points count.  Byte i is removed exactly when it is 03 and
+ * the two bytes in front of it are 00 00.  out: the RBSP bytes, *out_bytes their number; segment_rbsp_bytes[i] (may be NULL) = segment_bytes[i] less the removed bytes
+ * whose escaped position lies in segment i (an 03 exactly at a boundary belongs to the segment that starts there).  violations (may be NULL): the positions a conforming
+ * NAL unit cannot hold -- a byte <= 2 behind two or more zeros, a byte > 3 directly behind a removed 03 (the two asserts of :61 and :72); the output is the rule's all the
+ * same.  When *out_bytes exceeds out_capacity the call returns HOP_ERR_ARG, *out_bytes still the bytes needed, nothing stored at or past out + out_capacity.  An empty
+ * segment, no segment, a lookback outside 0..2: HOP_ERR_ARG.
+ * Three launches (csrc/k_stream.hip; hop_profile_*: HOP_K_UNESCAPE): count, scan, compact over chunks of 4096 bytes.  The predicate looks two bytes back and one ahead, so
+ * unlike the escape direction no chunk needs a carry from the one in front of it. */
+int hop_rbsp_unescape(hop_ctx* ctx, const uint8_t* escaped, const uint32_t* segment_bytes, int32_t n_segments, int32_t lookback, uint8_t* out, size_t out_capacity,
+                      size_t* out_bytes, uint32_t* segment_rbsp_bytes, uint32_t* violations);
+/* host only: the same as the sequential rule -- the yardstick of the device entry; the parameter sets, the slice header and the SEI are unescaped with it */
+int hop_rbsp_unescape_host(const uint8_t* escaped, const uint32_t* segment_bytes, int32_t n_segments, int32_t lookback, uint8_t* out, size_t out_capacity,
+                           size_t* out_bytes, uint32_t* segment_rbsp_bytes, uint32_t* violations);
+/* What an access unit says about itself: the picture's geometry, the parameters hop_access_unit_write would take to write it again, and where its slice data lies. */
+typedef struct {
+  int32_t pic_w, pic_h, bit_depth;
+  hop_stream_params params;     /* plain_intra = !vps_holo_extension_flag, slice_type 3 with the extension else 2, mi_size as the VPS carries it (0 without the extension),
+                                   qp = 26 + init_qp_minus26 + slice_qp_delta, wpp from the PPS, the SAO flags from the slice header (0 when the SPS switches SAO off),
+                                   poc 0 for IDR else pic_order_cnt_lsb, parameter_sets: whether this access unit carried them, hash: 0 without the SEI else hash_type + 1 */
+  int32_t nal_type;             /* of the VCL unit */
+  int32_t n_substreams;
+  int32_t header_bytes;         /* the ESCAPED bytes of the NAL unit header and the slice header: where the slice data starts in the VCL unit */
+} hop_stream_info;
+/* replaces: the byte stream cut of AnnexBread.cpp (byteStreamNALUnit), read and readNalUnitHeader (NALread.cpp:52-145; the cabac_zero_words cut :79-94), TDecCavlc::parseVPS /
+ * parseSPS / parsePPS / parsePTL / parseSliceHeader (TDecCAVLC.cpp, with the entry-point adjustment :1324-1355) and SEIReader::xParseSEIDecodedPictureHash (SEIread.cpp) for
+ * ONE access unit of the streams hop_access_unit_write writes: the mirror image of that entry.  au: the Annex B bytes of one access unit (hop_annexb_access_unit finds its
+ * end).  active: the info an earlier access unit of the same sequence gave, or NULL; required when this one carries no parameter sets, and when it carries them they must
+ * agree with it.  Outputs: info; data: the slice data's RBSP, the substreams back to back -- exactly what hop_slice_data_parse takes and hop_slice_data_write returns --,
+ * *data_bytes its length; substream_bytes[0 .. n_substreams); digest: the SEI's three digests laid out as hop_picture_hash returns them (the checksum and the CRC in their
+ * leading bytes, then zeros; all zero without an SEI).
+ * The reader accepts what the writer writes: every element write_vps / write_sps / write_pps / the slice header emit as a constant must have that value, anything else is
+ * HOP_ERR_ARG with hop_last_error naming the element (the device decoder has no other configuration); profile_tier_level and the level are read and ignored; SEI payloads
+ * other than the decoded picture hash are skipped by their length; a CRC hash is reported (hash 2) with its digest.
+ * Refused, HOP_ERR_ARG: NULL arguments; no VCL unit or more than one; a unit that ends inside an element; entry points that sum past the payload; an empty substream;
+ * n_substreams other than the picture's CTU rows (wpp) or 1; more substreams than max_substreams; active missing or contradicting; dimensions or a bit depth other than
+ * the context's; an emulation-prevention violation in the slice data; a sharded or stacked context.  Every read is bounded by au_bytes; data_capacity is a hard bound: when
+ * the slice data does not fit, HOP_ERR_ARG with *data_bytes the bytes needed.
+ * NAL header, parameter sets, slice header and SEI are parsed on the host from a host-unescaped prefix, which keeps the map back to escaped positions (header_bytes is exact
+ * when the header itself holds an 03, :1329-1335).  The slice data behind it is unescaped by hop_rbsp_unescape's kernels over the uploaded NAL unit, the segments from the
+ * entry points, the lookback into the header. */
+int hop_access_unit_read(hop_ctx* ctx, const uint8_t* au, size_t au_bytes, const hop_stream_info* active, hop_stream_info* info, uint8_t* data, size_t data_capacity,
+                         size_t* data_bytes, uint32_t* substream_bytes, int32_t max_substreams, uint8_t (*digest)[16]);
+/* host only: the same with the sequential rule over the slice data; no context, so no comparison with one and no error text.  The yardstick of the device entry and what
+ * the CPU tests and tools/stream_read_check.cpp drive. */
+int hop_access_unit_read_host(const uint8_t* au, size_t au_bytes, const hop_stream_info* active, hop_stream_info* info, uint8_t* data, size_t data_capacity,
+                              size_t* data_bytes, uint32_t* substream_bytes, int32_t max_substreams, uint8_t (*digest)[16]);
+/* host only: *au_bytes = the length of the first access unit of an Annex B stream -- parameter sets and other prefix units, one VCL unit, its suffix SEIs (type 40), up
+ * to the start code (with its zero bytes) of the unit that opens the next one, or the stream's end.  HOP_ERR_ARG: NULL, or no start code in the stream. */
+int hop_annexb_access_unit(const uint8_t* stream, size_t bytes, size_t* au_bytes);
+/* replaces: TDecTop::decode for one access unit (TLibDecoder/TDecTop.cpp: xDecodeSlice, executeLoopFilters) with the hash check of TAppDecTop (calcAndPrintHashStatus):
+ * bytes in, picture resident.  In order: hop_access_unit_read's work; the parser (the unescaped substreams go from the compact kernel's output to the parser's kernels
+ * without visiting the host; only their sizes come back, for the parser's host-side checks); hop_decode_frame; hop_deblock_frame; hop_sao_reconstruct_params and
+ * hop_sao_apply when an SAO flag is set; the hash of the result against the SEI's -- MD5 on the host path of hop_picture_hash, the checksum by its device pass.
+ * hash_match[plane]: 1 equal, 0 different, -1 not checked (no SEI, or CRC).  A mismatch is not an error of the call.  parts (256 per CTU), levels (6144 per CTU) and
+ * sao_coded (3 per CTU) may each be NULL.  Afterwards hop_recon_download gives the picture.  Refusals as hop_access_unit_read, hop_slice_data_parse and hop_decode_frame;
+ * a parse error (HOP_ERR_ARG naming substream and CTU) leaves the context usable. */
+int hop_access_unit_decode(hop_ctx* ctx, const uint8_t* au, size_t au_bytes, const hop_stream_info* active, hop_stream_info* info, int32_t hash_match[3],
+                           hop_cu_part* parts, int32_t* levels, hop_sao_param* sao_coded);
+
 /* ---- profiling (bench.py roofline): HIP events around every kernel launch on the context stream ---- */
 #define HOP_K_SS_SEARCH 0
 #define HOP_K_FRAC      1
@@ -928,7 +991,8 @@ int hop_picture_hash(hop_ctx* ctx, int method, uint8_t (*digest)[16]);
 #define HOP_K_PARSE     23    /* hop_slice_data_parse: the launches of the parser (units: CTUs) */
 #define HOP_K_ESCAPE    24    /* hop_rbsp_escape / hop_access_unit_write: the count, scan and scatter launches (units: bytes) */
 #define HOP_K_PICHASH   25    /* hop_picture_hash / hop_access_unit_write: the checksum pass (units: samples) */
-#define HOP_K_COUNT     26
+#define HOP_K_UNESCAPE  26    /* hop_rbsp_unescape / hop_access_unit_read / hop_access_unit_decode: the count, scan and compact launches (units: bytes) */
+#define HOP_K_COUNT     27
 int hop_profile_enable(hop_ctx* ctx, int on);
 /* waits for the stream, then reports launches, summed kernel time and units (PUs/CUs/jobs) since the last reset */
 int hop_profile_read(hop_ctx* ctx, int kernel, uint64_t* launches, double* total_ms, uint64_t* units);
