@@ -24,7 +24,8 @@ struct LeafShared {
 // vector-memory load on the dependent path).  As a function the loops get a register allocation of their own -- that of k_turd_fused_small, which holds the same code in 41
 // registers without a stack -- and the caller's live state is saved once around the call.  No barrier inside: the call may stand under `if (tid == 0)`.  L is the caller's
 // LeafShared / LeafSmallShared in LDS (hopd_lds: the loops address it with ds_* instructions, not flat_*), every other pointer is HBM.
-// MAXLOG2 = 5: a 32x32 unit's RDOQ work area is its slot of `work` in HBM; smaller units use L.work.
+// MAXLOG2 = 5: a 32x32 unit's RDOQ work area is its slot of `work` in HBM; smaller units use L.work.  The counted bits read the workgroup's bin table (cab_bin_fill at the
+// kernel's entry).
 template <class SH, int MAXLOG2>
 __device__ __noinline__ static void leaf_serial(SH* Lg, const int j, const int LOG2, const hop_tu_rd_job* jobs, const int n, const hop_cabac_ctx* ctx_in, const int64_t* coef_off,
                                                 uint32_t* as, unsigned long long* fr, hop_rdoq_job* rq, hop_coeff_bits_job* cb, char* work) {
@@ -81,6 +82,7 @@ __global__ __launch_bounds__(256) void k_turd_fused(const hop_tu_rd_job* __restr
                                                     hop_rdoq_job* __restrict__ rq, hop_coeff_bits_job* __restrict__ cb, char* __restrict__ work,
                                                     hop_tu_rd_result* __restrict__ res, int16_t* __restrict__ rec_y, int16_t* __restrict__ rec_cb, int16_t* __restrict__ rec_cr) {
   __shared__ LeafShared L;
+  cab_bin_fill();                                                     // the counted bits' bin table (all threads; the barrier is inside)
   turd_fused_body(L, blockIdx.x, jobs, n, pic, ctx_in, coef_off, entropy_bits, scans, coef, levels, zs, ns, as, fr, rq, cb, work, res, rec_y, rec_cb, rec_cr);
 }
 
@@ -134,6 +136,7 @@ __global__ __launch_bounds__(64) void k_turd_fused_small(const hop_tu_rd_job* __
                                                          hop_rdoq_job* __restrict__ rq, hop_coeff_bits_job* __restrict__ cb, char* __restrict__ work,
                                                          hop_tu_rd_result* __restrict__ res, int16_t* __restrict__ rec_y, int16_t* __restrict__ rec_cb, int16_t* __restrict__ rec_cr) {
   __shared__ LeafSmallShared L;
+  cab_bin_fill();                                                     // (before the empty slot's return: every thread reaches its barrier)
   const int j = blockIdx.x, tid = threadIdx.x;
   const hop_tu_rd_job jb = jobs[j];
   if (jb.log2_size < 2 || jb.log2_size > 3) return;                   // an empty slot; (larger TUs never come here: size_hint 1)

@@ -8,10 +8,10 @@
 #define RQ_SBH_THRESHOLD 4
 #define RQ_SCAN_SET_SIZE 16
 
-static __constant__ int c_rq_quant_scales[6] = { 26214, 23302, 20560, 18396, 16384, 14564 };      // TComRom.cpp:164-167
-static __constant__ int c_rq_inv_quant_scales[6] = { 40, 45, 51, 57, 64, 72 };                     // :169-172
-static __constant__ uint8_t c_rq_group_idx[32] = { 0,1,2,3,4,4,5,5,6,6,6,6,7,7,7,7,8,8,8,8,8,8,8,8,9,9,9,9,9,9,9,9 };   // :353
-static __constant__ uint8_t c_rq_ctx_ind_map[16] = { 0, 1, 4, 5, 2, 3, 4, 5, 6, 6, 8, 8, 7, 7, 8, 8 };
+// The quantiser scales (TComRom.cpp:164-172), g_uiGroupIdx (:353) and the 4x4 block's significance contexts are arithmetic on packed constants (hop_cabac_tab.h, each
+// checked against its table at compile time): as __constant__ arrays indexed by a lane's register they were a vector-memory load per 4x4 position and two per non-zero
+// level of the last-position pass, on the lane's dependent path.
+#include "hop_cabac_tab.h"
 
 // scan tables, built on the host (hop_rdoq_build_scans) and kept in device memory: scan[s][log2-2] at offset
 // s*1360 + {0,16,80,336}; coefficient-group scans cg[s][log2-2] at 4080 + s*85 + {0,1,5,21}
@@ -92,7 +92,7 @@ __device__ static inline uint32_t rq_sig_cg_ctx(unsigned long long cgFlag, uint3
 }
 __device__ static inline int rq_sig_ctx_inc(int patternSigCtx, int scanIdx, int posX, int posY, int log2BlockSize, bool is_luma) {
   if (posX + posY == 0) return 0;
-  if (log2BlockSize == 2) return c_rq_ctx_ind_map[4 * posY + posX];
+  if (log2BlockSize == 2) return hop_ctx_ind_map(4 * posY + posX);
   const int offset = log2BlockSize == 3 ? (scanIdx == RQ_SCAN_DIAG ? 9 : 15) : (is_luma ? 21 : 12);
   const int xs = posX & 3, ys = posY & 3;
   int cnt;
@@ -103,7 +103,7 @@ __device__ static inline int rq_sig_ctx_inc(int patternSigCtx, int scanIdx, int 
   return ((is_luma && ((posX >> 2) + (posY >> 2)) > 0) ? 3 : 0) + offset + cnt;
 }
 __device__ static inline double rq_rate_last(const hop_estbits* eb, double lambda, uint32_t posX, uint32_t posY) {
-  const uint32_t ctxX = c_rq_group_idx[posX], ctxY = c_rq_group_idx[posY];
+  const uint32_t ctxX = (uint32_t)hop_group_idx((int)posX), ctxY = (uint32_t)hop_group_idx((int)posY);
   double cost = (double)(eb->lastXBits[ctxX] + eb->lastYBits[ctxY]);
   if (ctxX > 3) cost += 32768.0 * (double)((ctxX - 2) >> 1);
   if (ctxY > 3) cost += 32768.0 * (double)((ctxY - 2) >> 1);
@@ -132,7 +132,7 @@ __device__ static void rdoq_tu(const hop_rdoq_job& jb, const hop_estbits* __rest
   const int per = jb.qp_scaled / 6, rem = jb.qp_scaled % 6;
   const int transformShift = 15 - jb.bit_depth - LOG2;                  // MAX_TR_DYNAMIC_RANGE - bitDepth - log2
   const int qBits = 14 + per + transformShift;                          // QUANT_SHIFT + per + shift
-  const int q = c_rq_quant_scales[rem];
+  const int q = hop_quant_scale(rem);
   const double errScale = ldexp((double)(1 << 15), -2 * transformShift);  // (1 << SCALE_BITS) * pow(2.0, -2.0*iTransformShift): exact
   const double dTemp = errScale / q / q / (1 << (2 * (jb.bit_depth - 8)));
   const double lambda = jb.lambda;
@@ -303,7 +303,7 @@ __device__ static void rdoq_tu(const hop_rdoq_job& jb, const hop_estbits* __rest
   // ---- sign bit hiding, :1883-1998 ----
   if (lastScanPos >= 0 && jb.sign_hide && absSum >= 2) {
     // Int arithmetic in the reference: inv*inv*(1<<(2*per)) wraps for per >= 10; reproduced as wrapping 32-bit
-    const int32_t prod = (int32_t)((uint32_t)(c_rq_inv_quant_scales[rem] * c_rq_inv_quant_scales[rem]) * (uint32_t)(1u << ((2 * per) & 31)));
+    const int32_t prod = (int32_t)((uint32_t)(hop_inv_quant_scale(rem) * hop_inv_quant_scale(rem)) * (uint32_t)(1u << ((2 * per) & 31)));
     const long long rdFactor = (long long)((double)prod / lambda / 16 / (1 << (2 * (jb.bit_depth - 8))) + 0.5);
     int lastCG = -1;
     for (int subSet = lastScanPos >> 4; subSet >= 0; subSet--) {        // the groups above hold no level

@@ -30,7 +30,7 @@ struct RqtWork {                                                      // per CU:
 // the time of ONE CU only when every CU has a wave of its own.  rqt_grid() picks the launch; the kernel tells the two apart by its grid.
 // CONTRACT of every `template <class LDS>` body of this file (and of cb_code_tu / cb_code_tu_at): `sh` must be a __shared__ object (CabacLds or CabacLds1).  The bodies the
 // compiler makes functions of their own say so to it (hopd_lds, hop_dev.h: an assumption, not a check) -- instantiated on a lane-private or HBM object they would be
-// miscompiled silently.
+// miscompiled silently.  A kernel that instantiates them on CabacLds1 fills the workgroup's bin table first (cab_bin_fill, k_cabac.hip): CBIN reads it.
 #define RQT_LANE_OR_BLOCK(n_) const bool spread_ = (n_) > 1 && gridDim.x == (unsigned)(n_); if (spread_ && threadIdx.x) return; \
                               const int lane = spread_ ? 0 : (int)threadIdx.x, i = spread_ ? (int)blockIdx.x : (int)(blockIdx.x * 64 + threadIdx.x)
 // (a wave per CU needs one column of context states: CabacLds1, 204 bytes -- a compute unit then holds 32 such CUs instead of 12)
@@ -165,6 +165,7 @@ __global__ __launch_bounds__(64) void k_rqt_single(RqtClass k, RqtNode nd, const
                                                    RqtWork* __restrict__ work, const hop_tu_rd_result* __restrict__ tr, const hop_tu_rd_result* __restrict__ tr2,
                                                    int32_t* __restrict__ coef, size_t ts_base, const uint16_t* __restrict__ scans) {
   __shared__ LDS sh;
+  cab_bin_fill_for<LDS>();                                           // (all threads, before the lanes part: the one-lane form's bin table, with its barrier)
   RQT_LANE_OR_BLOCK(n);
   if (i >= n) return;                                                // no barrier in this kernel
   rqt_single_body(sh, lane, i, k, nd, jobs, cur, root, test, res, work, tr, tr2, coef, ts_base, scans);
@@ -251,6 +252,7 @@ __global__ __launch_bounds__(64) void k_rqt_close(RqtClass k, RqtNode nd, const 
                                                   const hop_cabac_ctx* __restrict__ root, const hop_cabac_ctx* __restrict__ test, hop_rqt_result* __restrict__ res,
                                                   RqtWork* __restrict__ work, const int32_t* __restrict__ coef, const uint16_t* __restrict__ scans) {
   __shared__ LDS sh;
+  cab_bin_fill_for<LDS>();                                           // (all threads, before the lanes part: the one-lane form's bin table, with its barrier)
   RQT_LANE_OR_BLOCK(n);
   if (i >= n) return;
   rqt_close_body(sh, lane, i, k, nd, jobs, cur, root, test, res, work, coef, scans);
@@ -600,6 +602,7 @@ __global__ __launch_bounds__(64) void k_cu_bits(RqtClass k, int n, const hop_rqt
                                                 uint32_t* __restrict__ bits_out, uint32_t* __restrict__ skipped_out, hop_cabac_ctx* __restrict__ ctx_out,
                                                 hop_cabac_cu_ctx* __restrict__ cu_out, const uint16_t* __restrict__ scans) {
   __shared__ LDS sh;
+  cab_bin_fill_for<LDS>();                                           // (all threads, before the lanes part: the one-lane form's bin table, with its barrier)
   RQT_LANE_OR_BLOCK(n);
   if (i >= n) return;
   cu_bits_body(sh, lane, i, k, jobs, syn, res, coef, ctx_in, cu_in, bits_out, skipped_out, ctx_out, cu_out, scans);
@@ -713,6 +716,7 @@ __global__ __launch_bounds__(64) void k_intra_cu_bits(RqtClass k, int n, const h
                                                       const hop_cabac_cu_ctx* __restrict__ cu_in, uint32_t* __restrict__ bits_out, hop_cabac_ctx* __restrict__ ctx_out,
                                                       hop_cabac_cu_ctx* __restrict__ cu_out, const uint16_t* __restrict__ scans) {
   __shared__ LDS sh;
+  cab_bin_fill_for<LDS>();                                           // (all threads, before the lanes part: the one-lane form's bin table, with its barrier)
   RQT_LANE_OR_BLOCK(n);
   if (i >= n) return;
   const int ci = jobs[i].ctx_index;
@@ -895,6 +899,7 @@ __global__ __launch_bounds__(64) void k_irqt_single(RqtClass k, RqtNode nd, cons
                                                     int16_t* __restrict__ rec, int pitch, const int16_t* __restrict__ park, const uint16_t* __restrict__ scans,
                                                     const uint8_t* __restrict__ active) {
   __shared__ LDS sh;
+  cab_bin_fill_for<LDS>();                                           // (all threads, before the lanes part: the one-lane form's bin table, with its barrier)
   RQT_LANE_OR_BLOCK(n);
   if (i >= n) return;
   irqt_single_body(sh, lane, i, k, nd, jobs, syn, opt, cur, cucur, root, curoot, test, cutest, res, work, tr, tr2, coef, ts_base, rec, pitch, park, scans, active);
@@ -933,6 +938,7 @@ __global__ __launch_bounds__(64) void k_irqt_close(RqtClass k, RqtNode nd, const
                                                    hop_rqt_result* __restrict__ res, IrqWork* __restrict__ work, const int32_t* __restrict__ coef, const uint16_t* __restrict__ scans,
                                                    const uint8_t* __restrict__ active) {
   __shared__ LDS sh;
+  cab_bin_fill_for<LDS>();                                           // (all threads, before the lanes part: the one-lane form's bin table, with its barrier)
   RQT_LANE_OR_BLOCK(n);
   if (i >= n) return;
   irqt_close_body(sh, lane, i, k, nd, jobs, syn, cur, cucur, root, curoot, test, cutest, res, work, coef, scans, active);
@@ -1336,6 +1342,7 @@ __global__ __launch_bounds__(64) void k_ic_single(RqtClass k, RqtNode nd, int co
                                                   const hop_tu_rd_result* __restrict__ tr2, int32_t* __restrict__ coef, size_t ts_base, int16_t* __restrict__ rec, int pitch,
                                                   const int16_t* __restrict__ park, const uint16_t* __restrict__ scans) {
   __shared__ LDS sh;
+  cab_bin_fill_for<LDS>();                                           // (all threads, before the lanes part: the one-lane form's bin table, with its barrier)
   RQT_LANE_OR_BLOCK(n);
   if (i >= n) return;
   ic_single_body(sh, lane, i, k, nd, comp, jobs, syn, opt, cur, root, res, work, tr, tr2, coef, ts_base, rec, pitch, park, scans);
@@ -1370,6 +1377,7 @@ __global__ __launch_bounds__(64) void k_ic_bits(RqtClass k, const hop_rqt_job* _
                                                 const hop_cabac_ctx* __restrict__ ctx_in, const hop_cabac_cu_ctx* __restrict__ cu_in, const hop_rqt_result* __restrict__ res,
                                                 IcWork* __restrict__ work, const int32_t* __restrict__ coef, const uint16_t* __restrict__ scans) {
   __shared__ LDS sh;
+  cab_bin_fill_for<LDS>();                                           // (all threads, before the lanes part: the one-lane form's bin table, with its barrier)
   RQT_LANE_OR_BLOCK(n);
   if (i >= n) return;
   ic_bits_body(sh, lane, i, k, jobs, syn, ctx_in, cu_in, res, work, coef, scans);
@@ -1563,6 +1571,7 @@ __global__ __launch_bounds__(64) void k_intra_cu_total(RqtClass k, int n, const 
                                                        double* __restrict__ cost_out, hop_cabac_ctx* __restrict__ ctx_out, hop_cabac_cu_ctx* __restrict__ cu_out,
                                                        const uint16_t* __restrict__ scans) {
   __shared__ LDS sh;
+  cab_bin_fill_for<LDS>();                                           // (all threads, before the lanes part: the one-lane form's bin table, with its barrier)
   RQT_LANE_OR_BLOCK(n);
   if (i >= n) return;
   intra_cu_total_body(sh, lane, i, k, jobs, syn, res, coef, ctx_in, cu_in, dist, bits_out, cost_out, ctx_out, cu_out, scans);

@@ -81,7 +81,7 @@ __device__ static void walk_inter_leaves(const InterWalk& A, InterLeafShared& L,
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, n3 = 3 * A.n;
   for (int c = 0; c < ncomp; c++) {
     if (A.tuj[3 * i + c].log2_size <= 3) continue;                      // (uniform over the workgroup)
-    turd_fused_body(L.u.big, 3 * i + c, A.tuj, n3, A.pic, A.root[d], A.off, A.entropy_bits, A.scans, A.lcoef, A.coef, A.zs, A.ns, A.as, A.fr, A.rq, A.cb, A.lwork, A.tr,
+    turd_fused_body(L.u.big, 3 * i + c, A.tuj, n3, A.pic, A.root[d], A.off, A.entropy_bits, s_scan_tables, A.lcoef, A.coef, A.zs, A.ns, A.as, A.fr, A.rq, A.cb, A.lwork, A.tr,
                     A.rec_y, A.rec_cb, A.rec_cr);
     __syncthreads();
   }
@@ -89,12 +89,12 @@ __device__ static void walk_inter_leaves(const InterWalk& A, InterLeafShared& L,
   // one after the other (HOP_WALK_WAVE_LEAVES=0)
   for (int c = 0; c < ncomp; c++) {
     if (A.tuj[3 * i + c].log2_size > 3) continue;
-    turd_fused_body(L.u.big, 3 * i + c, A.tuj, n3, A.pic, A.root[d], A.off, A.entropy_bits, A.scans, A.lcoef, A.coef, A.zs, A.ns, A.as, A.fr, A.rq, A.cb, A.lwork, A.tr,
+    turd_fused_body(L.u.big, 3 * i + c, A.tuj, n3, A.pic, A.root[d], A.off, A.entropy_bits, s_scan_tables, A.lcoef, A.coef, A.zs, A.ns, A.as, A.fr, A.rq, A.cb, A.lwork, A.tr,
                     A.rec_y, A.rec_cb, A.rec_cr);
     __syncthreads();
   }
   for (int t = 0; t < nts; t++) {
-    turd_fused_body(L.u.big, 3 * i + t, A.tuj2, n3, A.pic, A.root[d], A.off2, A.entropy_bits, A.scans, A.lcoef, A.coef, A.zs + n3, A.ns + n3, A.as + n3, A.fr + n3, A.rq + n3, A.cb + n3,
+    turd_fused_body(L.u.big, 3 * i + t, A.tuj2, n3, A.pic, A.root[d], A.off2, A.entropy_bits, s_scan_tables, A.lcoef, A.coef, A.zs + n3, A.ns + n3, A.as + n3, A.fr + n3, A.rq + n3, A.cb + n3,
                     A.lwork, A.tr2, A.rec_y, A.rec_cb, A.rec_cr);
     __syncthreads();
   }
@@ -110,7 +110,7 @@ __device__ static void walk_inter_leaves(const InterWalk& A, InterLeafShared& L,
     // ONE call site that every wave reaches with all its lanes (the tables picked per wave): the first form -- two calls under `if (ts)`, the body a function of its own
     // called from wave-divergent control flow -- faulted on the device (HSA_STATUS_ERROR_MEMORY_APERTURE_VIOLATION)
     const int sh = ts ? n3 : 0;
-    turd_fused_small_wave_body(L.u.small[wave], lane, j, ts ? A.tuj2 : A.tuj, n3, A.pic, A.root[d], ts ? A.off2 : A.off, A.entropy_bits, A.scans, A.lcoef, A.coef, A.zs + sh, A.ns + sh,
+    turd_fused_small_wave_body(L.u.small[wave], lane, j, ts ? A.tuj2 : A.tuj, n3, A.pic, A.root[d], ts ? A.off2 : A.off, A.entropy_bits, s_scan_tables, A.lcoef, A.coef, A.zs + sh, A.ns + sh,
                                A.as + sh, A.fr + sh, A.rq + sh, A.cb + sh, ts ? A.tr2 : A.tr, A.rec_y, A.rec_cb, A.rec_cr);
     __syncthreads();
   }
@@ -120,6 +120,7 @@ __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_inter_walk(InterWa
   __shared__ InterLeafShared IL;
   LeafShared& L = IL.u.big;
   __shared__ CabacLds1 sh1;
+  walk_tables_fill(A.scans);                                             // the one-lane coders' bin table and the scan tables into LDS: all threads, first thing, the barrier inside
   const int i = blockIdx.x, tid = threadIdx.x;
   const RqtClass k = A.k;
   const int parts = 1 << (2 * (k.log2_cu - 2));
@@ -141,7 +142,7 @@ __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_inter_walk(InterWa
       __syncthreads();
       if (nd.check_full) {
         walk_inter_leaves(A, IL, i, d, ncomp, nts);
-        if (tid == 0) rqt_single_body(sh1, 0, i, k, nd, A.jobs, A.cur, A.root[d], A.test[d], A.res, A.work, A.tr + sh_c, A.tr2 + sh_t, A.coef, A.ts_base, A.scans);
+        if (tid == 0) rqt_single_body(sh1, 0, i, k, nd, A.jobs, A.cur, A.root[d], A.test[d], A.res, A.work, A.tr + sh_c, A.tr2 + sh_t, A.coef, A.ts_base, s_scan_tables);
         __syncthreads();
       }
       if (!nd.check_split) { sp--; continue; }
@@ -153,7 +154,7 @@ __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_inter_walk(InterWa
       sp++;
       continue;
     }
-    if (tid == 0) rqt_close_body(sh1, 0, i, k, nd, A.jobs, A.cur, A.root[d], A.test[d], A.res, A.work, A.coef, A.scans);
+    if (tid == 0) rqt_close_body(sh1, 0, i, k, nd, A.jobs, A.cur, A.root[d], A.test[d], A.res, A.work, A.coef, s_scan_tables);
     __syncthreads();
     sp--;
   }
@@ -169,7 +170,7 @@ __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_inter_walk(InterWa
   if (tid == 0) {
     fin_sum_body(i, A.jobs, A.nj, A.ftuj, A.fsse, A.fin);
     // ---- the CU's syntax bits from the CI_CURR_BEST state, the cost ----
-    cu_bits_body(sh1, 0, i, k, A.jobs, A.syn, A.res, A.coef_out, A.ctx_in, A.cu_in, A.bits, A.skipped, A.ctx_out, A.cu_out, A.scans);
+    cu_bits_body(sh1, 0, i, k, A.jobs, A.syn, A.res, A.coef_out, A.ctx_in, A.cu_in, A.bits, A.skipped, A.ctx_out, A.cu_out, s_scan_tables);
     A.cost[i] = rqt_cost(A.bits[i], A.fin[i].dist[0] + A.fin[i].dist[1] + A.fin[i].dist[2], A.jobs[i].lambda_rd);
   }
 }
@@ -281,7 +282,7 @@ __device__ static inline IwView iw_view(const IntraWalk& A) {          // the ca
   return W;
 }
 
-#define IW_LEAF(JOBS, CTX, OFF, LEVELS, RES) turd_fused_body(L.leaf, i, JOBS, W.n, W.pic, CTX, OFF, A.entropy_bits, A.scans, A.lcoef, LEVELS, A.zs, A.ns, A.as, A.fr, A.rq, A.cb, A.lwork, RES, \
+#define IW_LEAF(JOBS, CTX, OFF, LEVELS, RES) turd_fused_body(L.leaf, i, JOBS, W.n, W.pic, CTX, OFF, A.entropy_bits, s_scan_tables, A.lcoef, LEVELS, A.zs, A.ns, A.as, A.fr, A.rq, A.cb, A.lwork, RES, \
                                                              W.rec_y, W.rec_cb, W.rec_cr)
 
 // one pass of xRecurIntraCodingQT over the PU (hop_launch_intra_rqt with the pass's direction in syn): results into A.tmp / A.coef_tmp
@@ -317,7 +318,7 @@ __device__ static __forceinline__ void walk_intra_rqt(const IntraWalk& A, const 
         __syncthreads();
         if (nd.check_split) { irqt_copy_body(i, tid, 256, 0, k, nd, W.jobs, W.syn, A.irwork, W.rec_y, pitch, A.recl, A.park, nullptr); __syncthreads(); }
         if (tid == 0) irqt_single_body(sh1, 0, i, k, nd, W.jobs, W.syn, W.opt, A.cur, A.cucur, A.root[d], A.curoot[d], A.test[d], A.cutest[d], W.tmp, A.irwork, A.tr, A.tr2, A.coef, A.ts_base,
-                                       W.rec_y, pitch, A.park, A.scans, nullptr);
+                                       W.rec_y, pitch, A.park, s_scan_tables, nullptr);
         __syncthreads();
       }
       if (!nd.check_split) { sp--; continue; }
@@ -329,7 +330,7 @@ __device__ static __forceinline__ void walk_intra_rqt(const IntraWalk& A, const 
       sp++;
       continue;
     }
-    if (tid == 0) irqt_close_body(sh1, 0, i, k, nd, W.jobs, W.syn, A.cur, A.cucur, A.root[d], A.curoot[d], A.test[d], A.cutest[d], W.tmp, A.irwork, A.coef, A.scans, nullptr);
+    if (tid == 0) irqt_close_body(sh1, 0, i, k, nd, W.jobs, W.syn, A.cur, A.cucur, A.root[d], A.curoot[d], A.test[d], A.cutest[d], W.tmp, A.irwork, A.coef, s_scan_tables, nullptr);
     __syncthreads();
     if (nd.check_full) { irqt_copy_body(i, tid, 256, 2, k, nd, W.jobs, W.syn, A.irwork, W.rec_y, pitch, A.recl, A.park, nullptr); __syncthreads(); }
     sp--;
@@ -345,7 +346,7 @@ __device__ static __forceinline__ void iw_luma_prep(const IntraWalk& A, WalkShar
   __syncthreads();
   intra_rough_body(L.intra, A.rj + i, A.pic, A.rec_y, A.satd + (size_t)i * 35);
   __syncthreads();
-  if (threadIdx.x == 0) intra_modes_body(i, A.mj, A.satd, A.mres);
+  if (threadIdx.x == 0) intra_modes_body<true>(i, A.mj, A.satd, A.mres);
   __syncthreads();
 }
 // the best mode again with the full tree, the better result kept, the decided PU into the picture (:2555-2660).  Where that pass repeats the winner it is left out, and the
@@ -400,7 +401,7 @@ __device__ static __forceinline__ void iw_chroma_mode(const IntraWalk& A, const 
           }
           IW_LEAF(A.tuj, A.ccur, A.off, A.ccoef, A.tr);
           __syncthreads();
-          if (tid == 0) ic_single_body(sh1, 0, i, k, nd, comp, W.jobs, W.csyn, W.opt, A.ccur, A.croot, W.res, A.icwork, A.tr, A.tr2, A.ccoef, A.ts_base, recc, pitch_c, A.cpark, A.scans);
+          if (tid == 0) ic_single_body(sh1, 0, i, k, nd, comp, W.jobs, W.csyn, W.opt, A.ccur, A.croot, W.res, A.icwork, A.tr, A.tr2, A.ccoef, A.ts_base, recc, pitch_c, A.cpark, s_scan_tables);
           __syncthreads();
         }
       }
@@ -417,7 +418,7 @@ __device__ static __forceinline__ void iw_chroma_mode(const IntraWalk& A, const 
     __syncthreads();
     sp--;
   }
-  if (tid == 0) ic_bits_body(sh1, 0, i, k, W.jobs, W.csyn, A.ctx_in, A.cu_in, W.res, A.icwork, A.ccoef, A.scans);
+  if (tid == 0) ic_bits_body(sh1, 0, i, k, W.jobs, W.csyn, A.ctx_in, A.cu_in, W.res, A.icwork, A.ccoef, s_scan_tables);
   __syncthreads();
 }
 __device__ static inline void iw_zero_ccoef(const IntraWalk& A, const int i) {
@@ -431,7 +432,7 @@ __device__ static inline void iw_total(const IntraWalk& A, CabacLds1& sh1, const
   if (threadIdx.x == 0) {
     const RqtClass k = A.k;                                              // (a copy: a reference into A handed to a function of its own would put the whole table on the stack)
     A.dist[i] = A.sres[i].dist + A.cres[i].dist;
-    intra_cu_total_body(sh1, 0, i, k, A.jobs, A.syn_out, A.res, A.coef_out, A.ctx_in, A.cu_in, A.dist, A.bits, A.cost, A.ctx_out, A.cu_out, A.scans);
+    intra_cu_total_body(sh1, 0, i, k, A.jobs, A.syn_out, A.res, A.coef_out, A.ctx_in, A.cu_in, A.dist, A.bits, A.cost, A.ctx_out, A.cu_out, s_scan_tables);
   }
 }
 
@@ -439,6 +440,7 @@ __device__ static inline void iw_total(const IntraWalk& A, CabacLds1& sh1, const
 __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_intra_walk(IntraWalk A) {
   __shared__ WalkShared L;
   __shared__ CabacLds1 sh1;
+  walk_tables_fill(A.scans);
   const int i = blockIdx.x, tid = threadIdx.x;
   const RqtClass k = A.k;
   const int pitch = A.pic.pic_w, pitch_c = A.pic.pic_w >> 1;
@@ -498,6 +500,7 @@ __device__ static inline IwView iw_virtual(const IntraWalk& A, const int v, cons
 
 __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_iw_begin(IntraWalk A) {
   __shared__ WalkShared L;
+  cab_bin_fill();                                                        // (intra_modes_body reads the bin table; no transform unit is coded here)
   const int i = blockIdx.x, tid = threadIdx.x;
   if (tid == 0) A.syn[i] = A.syn_in[i];
   { uint32_t* z = (uint32_t*)(A.res + i); for (int e = tid; e < (int)(sizeof(hop_rqt_result) / 4); e += 256) z[e] = 0; }
@@ -509,6 +512,7 @@ __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_iw_begin(IntraWalk
 __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_iw_cand(IntraWalk A, int pu) {
   __shared__ WalkShared L;
   __shared__ CabacLds1 sh1;
+  walk_tables_fill(A.scans);                                             // (before the return of a pass this CU's list does not have)
   const int i = blockIdx.x, pass = blockIdx.y, tid = threadIdx.x;
   const int cnt = (int)A.mres[i].n, n_max = A.num_full_rd + 2;
   if (pass >= cnt || pass >= n_max) return;
@@ -529,6 +533,7 @@ __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_iw_pick(IntraWalk 
   __shared__ WalkShared L;
   __shared__ CabacLds1 sh1;
   __shared__ int s_best;
+  walk_tables_fill(A.scans);
   const int i = blockIdx.x, tid = threadIdx.x;
   const RqtClass k = A.k;
   const int n_max = A.num_full_rd + 2, npu = A.nxn ? 4 : 1;
@@ -563,6 +568,7 @@ __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_iw_pick(IntraWalk 
 __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_iw_chroma(IntraWalk A) {
   __shared__ WalkShared L;
   __shared__ CabacLds1 sh1;
+  walk_tables_fill(A.scans);
   const int i = blockIdx.x, m = blockIdx.y, tid = threadIdx.x;
   const int v = i * A.P + m;
   const hop_rqt_job jb = A.jobs[i];
@@ -583,6 +589,7 @@ __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_iw_chroma(IntraWal
 __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_iw_finish(IntraWalk A) {
   __shared__ CabacLds1 sh1;
   __shared__ int s_best;
+  walk_tables_fill(A.scans);
   const int i = blockIdx.x, tid = threadIdx.x;
   const RqtClass k = A.k;
   if (tid == 0) {
