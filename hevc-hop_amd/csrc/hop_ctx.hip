@@ -274,7 +274,7 @@ int hop_ctx_create_view(hop_ctx* parent, hop_ctx** out) {
   *out = nullptr;
   hop_ctx* c = (hop_ctx*)calloc(1, sizeof(hop_ctx));
   c->pic_w = parent->pic_w; c->pic_h = parent->pic_h; c->bd_y = parent->bd_y; c->bd_c = parent->bd_c; c->device = parent->device;
-  c->stride_y = parent->stride_y; c->stride_c = parent->stride_c; c->sub_h = parent->sub_h; c->sub_pitch = parent->sub_pitch; c->slots = parent->slots; c->fused_leaf_max = parent->fused_leaf_max; c->walk_max = parent->walk_max; c->ss_families = parent->ss_families; c->lanes = 1; c->is_view = true;
+  c->stride_y = parent->stride_y; c->stride_c = parent->stride_c; c->sub_h = parent->sub_h; c->sub_pitch = parent->sub_pitch; c->slots = parent->slots; c->fused_leaf_max = parent->fused_leaf_max; c->walk_max = parent->walk_max; c->ss_families = parent->ss_families; c->row_limit = parent->row_limit; c->lanes = 1; c->is_view = true;
   c->org_y = parent->org_y; c->org_cb = parent->org_cb; c->org_cr = parent->org_cr;
   for (int k = 0; k < 3; k++) { c->ss_alloc[k] = parent->ss_alloc[k]; c->ss_buf[k] = parent->ss_buf[k]; c->ss00[k] = parent->ss00[k]; c->pred[k] = parent->pred[k]; c->rec[k] = parent->rec[k]; }
   c->entropy_bits = parent->entropy_bits; c->rdoq_scans = parent->rdoq_scans; c->have_orig = parent->have_orig; c->stash = parent->stash; c->stash_slots = parent->stash_slots; c->coefpic = parent->coefpic; c->coef_stash = parent->coef_stash;
@@ -309,6 +309,15 @@ int hop_ctx_set_slots(hop_ctx* c, int slots) {
 }
 
 int hop_set_fused_leaf(hop_ctx* c, int max_tus) { if (!c || max_tus < 0) return hop_set_err(c, HOP_ERR_ARG, "hop_set_fused_leaf: bad argument"); c->fused_leaf_max = max_tus; return HOP_OK; }
+
+// Raster-order visibility for the searches of a wavefront: while on, every read of the SS reference by hop_me_search, hop_pred_inter / hop_pred_cost
+// and hop_valid_pattern (and their *_device forms) finds the sentinel from the bottom of the CTU row that holds the PU's top-left sample on (hop_row_limit, hop_dev.h) --
+// what the reference, which has coded nothing below the current CTU row, finds there.  The resident samples are not touched; hop_decode_frame ignores the switch.
+int hop_ctx_set_row_limit(hop_ctx* c, int on) {
+  if (!c) return hop_set_err(c, HOP_ERR_ARG, "hop_ctx_set_row_limit: bad argument");
+  c->row_limit = on ? 1 : 0;
+  return HOP_OK;
+}
 
 int hop_stack_pitch(int sub_h) { return ((sub_h + 63) / 64) * 64 + 64 * ((2 * (HOP_MARGIN_Y + HOP_GUARD_ROWS) + 63) / 64); }
 int hop_ctx_set_stack(hop_ctx* c, int sub_h, int sub_pitch) {

@@ -29,6 +29,8 @@ struct hop_ctx : hop_lane {
   int slots;                         // hop_ctx_set_slots: the original, prediction and reconstruction pictures exist slots + 1 times, copy k at rows k * pic_h (0: once)
   int fused_leaf_max;                // hop_set_fused_leaf: leaf batches of up to this many TUs run as the one-kernel form (default 8192; 0 = always staged)
   int sub_h, sub_pitch;              // hop_ctx_set_stack: the picture is a stack of independent pictures of sub_h rows, origins sub_pitch rows apart (0, 0: one picture)
+  int row_limit;                     // hop_ctx_set_row_limit: reads of the SS reference see the sentinel from the bottom of the PU's CTU row on (raster-order visibility; default 0)
+  int enc_exact;                     // hop_encode_set_exact: 0 never called (HOP_ENCODE_EXACT decides), 1 on, -1 off
   // device pictures
   int16_t *org_y, *org_cb, *org_cr;  // original, pitch pic_w / pic_w/2, no margins
   int16_t *ss_alloc[3];              // allocations: HOP_GUARD_ROWS sentinel rows + padded plane + HOP_GUARD_ROWS
@@ -73,6 +75,7 @@ struct hop_pics {
   const int16_t* ss_y;  const int16_t* ss_cb;  const int16_t* ss_cr;   // at sample (0,0)
   int16_t* pred_y; int16_t* pred_cb; int16_t* pred_cr;
   int pic_w, pic_h, stride_y, stride_c, bd_y, bd_c;
+  int row_limit, sub_h, sub_pitch;   // hop_ctx_set_row_limit and the stack geometry it counts CTU rows in (hop_row_limit)
 };
 
 static inline hop_pics hop_make_pics(const hop_ctx* c) {
@@ -82,7 +85,23 @@ static inline hop_pics hop_make_pics(const hop_ctx* c) {
   p.pred_y = c->pred[0]; p.pred_cb = c->pred[1]; p.pred_cr = c->pred[2];
   p.pic_w = c->pic_w; p.pic_h = c->pic_h; p.stride_y = c->stride_y; p.stride_c = c->stride_c;
   p.bd_y = c->bd_y; p.bd_c = c->bd_c;
+  p.row_limit = c->row_limit; p.sub_h = c->sub_h; p.sub_pitch = c->sub_pitch;
   return p;
+}
+
+// hop_ctx_set_row_limit: the first luma row a PU whose top-left sample lies in row pu_y must not see -- the bottom of its CTU row, counted from the origin of its own
+// picture (a stacked context) -- or HOP_NO_ROW_LIMIT: the limit is off, or the CTU row is the picture's last (the rows below it are the bottom margin, which copies a
+// row above the limit).  A reference sample in row y (margin rows included: they copy the nearest picture row) reads as the sentinel iff y >= the limit; the chroma
+// limit is half of it.  In raster order nothing below the current CTU row has been coded (TEncSlice::compressSlice, TEncSlice.cpp:1000-1196).
+#define HOP_NO_ROW_LIMIT 0x3FFFFFFF
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+static inline int hop_row_limit(const hop_pics& pic, int pu_y) {
+  if (!pic.row_limit) return HOP_NO_ROW_LIMIT;
+  const int top = pic.sub_pitch ? (pu_y / pic.sub_pitch) * pic.sub_pitch : 0, ph = pic.sub_pitch ? pic.sub_h : pic.pic_h;
+  const int lim = top + (((pu_y - top) >> 6) + 1) * 64;
+  return lim < top + ph ? lim : HOP_NO_ROW_LIMIT;
 }
 
 #ifdef __HIPCC__

@@ -167,7 +167,7 @@ __device__ void dec_inter_cu(DecShared& sh, const DecArgs& A, const hop_cu_part*
     }
     __syncthreads();
     const hop_pred_job j = sh.pj;
-    for (int comp = 0; comp < 3; comp++) { pred_inter_body(sh.u.pr, j, comp, A.pic); __syncthreads(); }
+    for (int comp = 0; comp < 3; comp++) { pred_inter_body<false>(sh.u.pr, j, comp, A.pic); __syncthreads(); }
   }
   const int np = 1 << (2 * (log2cu - 2));
   for (int u = 0; u < np;) {
@@ -258,7 +258,7 @@ extern "C" int hop_decode_frame(hop_ctx* c, const hop_dec_params* p, const hop_c
   if (e != hipSuccess) return hop_set_err(c, HOP_ERR_DEVICE, "hop_decode_frame: upload: %s", hipGetErrorString(e));
   if (!p->plain_intra) { r = hop_launch_ssref_reset(c); if (r) return r; }
   A.parts = (const hop_cu_part*)b; A.levels = (const int32_t*)(b + o_levels);
-  A.pic = hop_make_pics(c); A.pic.org_y = A.pic.org_cb = A.pic.org_cr = nullptr;
+  A.pic = hop_make_pics(c); A.pic.org_y = A.pic.org_cb = A.pic.org_cr = nullptr;      // (hop_ctx_set_row_limit is an encoder's: k_dec_ctu instantiates pred_inter_body<false>, which has no limited reads at all)
   A.pic_tu = A.pic; A.pic_tu.org_y = A.pic.pred_y; A.pic_tu.org_cb = A.pic.pred_cb; A.pic_tu.org_cr = A.pic.pred_cr;
   for (int k = 0; k < 3; k++) { A.rec[k] = c->rec[k]; A.ss00[k] = c->ss00[k]; }
   A.wctu = wctu; A.commit = !p->plain_intra;

@@ -58,9 +58,17 @@ __global__ __launch_bounds__(NW * 64) void k_frac(const hop_pu_job* __restrict__
   const int mvx = rp->mv_int[0], mvy = rp->mv_int[1];
   {
     const int16_t* src = pic.ss_y + (ptrdiff_t)(jb.pu_y + mvy - 4) * pic.stride_y + (jb.pu_x + mvx - 4);
-    for (int i = tid; i < (H + 8) * (W + 8); i += NT) {
-      int r = i / (W + 8), c = i - r * (W + 8);
-      sh.win[r * FR_TP + c] = src[(ptrdiff_t)r * pic.stride_y + c];
+    const int lim_r = hop_row_limit(pic, jb.pu_y) - (jb.pu_y + mvy - 4);   // first window row at or below the row limit (hop_ctx_set_row_limit)
+    if (lim_r >= H + 8) {                                                 // the window ends above it (always, while the limit is off): uniform over the workgroup
+      for (int i = tid; i < (H + 8) * (W + 8); i += NT) {
+        int r = i / (W + 8), c = i - r * (W + 8);
+        sh.win[r * FR_TP + c] = src[(ptrdiff_t)r * pic.stride_y + c];
+      }
+    } else {
+      for (int i = tid; i < (H + 8) * (W + 8); i += NT) {
+        int r = i / (W + 8), c = i - r * (W + 8);
+        sh.win[r * FR_TP + c] = r >= lim_r ? (int16_t)HOP_NOT_VALID : src[(ptrdiff_t)r * pic.stride_y + c];
+      }
     }
     for (int i = tid; i < W * H; i += NT) {
       int r = i / W, c = i - r * W;

@@ -336,12 +336,23 @@ __global__ __launch_bounds__(NW * 64) void k_gt_search(const hop_pu_job* __restr
     // element (r,c) = sample(r,c) | sample(r,c+1) << HS  (the last column's partner is never used)
     {
       const int16_t* src = pic.ss_y + (ptrdiff_t)(pu_y + sy - H / 2) * pic.stride_y + (pu_x + sx - W / 2);
-      for (int i = tid; i < 4 * W * H; i += NT) {
-        int r = i / (2 * W), c = i - r * (2 * W);
-        int v0 = src[(ptrdiff_t)r * pic.stride_y + c];
-        int v1 = (c + 1 < 2 * W) ? src[(ptrdiff_t)r * pic.stride_y + c + 1] : 0;
-        v0 = min(maxVal, max(0, v0)); v1 = min(maxVal, max(0, v1));
-        sh.patch[r * PP + c] = (PT)((unsigned)v0 | ((unsigned)v1 << HS));
+      const int lim_r = hop_row_limit(pic, pu_y) - (pu_y + sy - H / 2);   // first patch row at or below the row limit (hop_ctx_set_row_limit)
+      if (lim_r >= 2 * H) {                                               // the patch ends above it (always, while the limit is off): uniform over the workgroup
+        for (int i = tid; i < 4 * W * H; i += NT) {
+          int r = i / (2 * W), c = i - r * (2 * W);
+          int v0 = src[(ptrdiff_t)r * pic.stride_y + c];
+          int v1 = (c + 1 < 2 * W) ? src[(ptrdiff_t)r * pic.stride_y + c + 1] : 0;
+          v0 = min(maxVal, max(0, v0)); v1 = min(maxVal, max(0, v1));
+          sh.patch[r * PP + c] = (PT)((unsigned)v0 | ((unsigned)v1 << HS));
+        }
+      } else {                                                            // rows from the limit on read as the sentinel, which the clamp turns into 0
+        for (int i = tid; i < 4 * W * H; i += NT) {
+          int r = i / (2 * W), c = i - r * (2 * W);
+          int v0 = r >= lim_r ? HOP_NOT_VALID : src[(ptrdiff_t)r * pic.stride_y + c];
+          int v1 = (c + 1 < 2 * W) ? (r >= lim_r ? HOP_NOT_VALID : src[(ptrdiff_t)r * pic.stride_y + c + 1]) : 0;
+          v0 = min(maxVal, max(0, v0)); v1 = min(maxVal, max(0, v1));
+          sh.patch[r * PP + c] = (PT)((unsigned)v0 | ((unsigned)v1 << HS));
+        }
       }
     }
     wg_sync<NW>();

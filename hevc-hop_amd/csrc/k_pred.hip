@@ -14,7 +14,7 @@
 __global__ __launch_bounds__(256) void k_pred_inter(const hop_pred_job* __restrict__ jobs, hop_pics pic) {
   __shared__ PredShared sh;
   const hop_pred_job jb = jobs[blockIdx.x];
-  pred_inter_body(sh, jb, blockIdx.y, pic);
+  pred_inter_body<true>(sh, jb, blockIdx.y, pic);
 }
 
 int hop_launch_pred(hop_ctx* c, int n, const hop_pred_job* d_jobs) {
@@ -118,7 +118,8 @@ __global__ __launch_bounds__(256) void k_distortion(const hop_dist_job* __restri
 // grid (jobs, 3).  Plane 0: the luma prediction into an LDS tile, its distortion against the original -> out[job]; the LAST candidate of a sequence also writes its tile to
 // the prediction picture.  Planes 1 / 2: the chroma prediction of the last candidate of each sequence into the picture (the other workgroups return at once) -- afterwards
 // the prediction picture holds the last candidate's prediction in all planes, as after the reference's loop.
-__global__ __launch_bounds__(256) void k_pred_cost(const int32_t* __restrict__ seq_of, const int32_t* __restrict__ first, const hop_pred_job* __restrict__ jobs,
+// (three workgroups per CU fit by LDS: the register allocator is held to the 168 VGPRs that lets them run, which it met by itself before the row-limited loops joined)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_pred_cost(const int32_t* __restrict__ seq_of, const int32_t* __restrict__ first, const hop_pred_job* __restrict__ jobs,
                                                    const int32_t* __restrict__ kinds, hop_pics pic, uint32_t* __restrict__ out) {
   __shared__ PredShared sh;
   __shared__ int16_t tile[64 * 64];
@@ -126,8 +127,8 @@ __global__ __launch_bounds__(256) void k_pred_cost(const int32_t* __restrict__ s
   const int j = blockIdx.x, comp = blockIdx.y, s = seq_of[j];
   const bool last = j == first[s + 1] - 1;
   const hop_pred_job jb = jobs[j];
-  if (comp) { if (last) pred_inter_body(sh, jb, comp, pic); return; }
-  pred_inter_body(sh, jb, 0, pic, tile);
+  if (comp) { if (last) pred_inter_body<true>(sh, jb, comp, pic); return; }
+  pred_inter_body<true>(sh, jb, 0, pic, tile);
   __syncthreads();
   hop_dist_job d; d.x = jb.pu_x; d.y = jb.pu_y + jb.dst_row_off; d.w = jb.w; d.h = jb.h; d.comp = 0; d.kind = kinds[s];
   const uint32_t v = distortion_body(acc, d, pic, tile);

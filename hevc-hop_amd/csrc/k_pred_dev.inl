@@ -5,19 +5,19 @@ static __constant__ int16_t c_taps4[8][4] = {
   { 0, 64, 0, 0 }, { -2, 58, 10, -2 }, { -4, 54, 16, -2 }, { -6, 46, 28, -4 }, { -4, 36, 36, -4 }, { -4, 28, 46, -6 }, { -2, 16, 54, -4 }, { -2, 10, 58, -2 } };
 
 // Uni-prediction sample at integer (x,y) of `src`, phase (xf,yf): TComPrediction.cpp:662-678 / :1272-1289.
-// NT = 8 (luma) or 4 (chroma).
-template <int NT>
-__device__ static inline int mc_sample(const int16_t* __restrict__ src, int stride, int x, int y, int xf, int yf, int bd) {
+// NT = 8 (luma) or 4 (chroma).  LIM: rows of `src` from lim_row on read as the sentinel (hop_ctx_set_row_limit); the unlimited form is the code it was.
+template <int NT, bool LIM>
+__device__ static inline int mc_sample(const int16_t* __restrict__ src, int stride, int x, int y, int xf, int yf, int bd, int lim_row = 0) {
   const int16_t* cx = NT == 8 ? c_taps8[xf] : c_taps4[xf];
   const int16_t* cy = NT == 8 ? c_taps8[yf] : c_taps4[yf];
   constexpr int HALF = NT / 2 - 1;
   const int headRoom = 14 - bd, maxVal = (1 << bd) - 1;
   const int16_t* p = src + (ptrdiff_t)y * stride + x;
-  if (xf == 0 && yf == 0) return p[0];                        // filterCopy(isFirst == isLast): plain copy, no clip
+  if (xf == 0 && yf == 0) return (LIM && y >= lim_row) ? HOP_NOT_VALID : p[0];   // filterCopy(isFirst == isLast): plain copy, no clip
   if (yf == 0 || xf == 0) {                                   // single pass, filter<N,*,true,true>: shift 6, offset 32, clip
     int sum = 0;
-    if (yf == 0) { for (int k = 0; k < NT; k++) sum += p[k - HALF] * cx[k]; }
-    else { for (int k = 0; k < NT; k++) sum += p[(ptrdiff_t)(k - HALF) * stride] * cy[k]; }
+    if (yf == 0) { for (int k = 0; k < NT; k++) sum += ((LIM && y >= lim_row) ? HOP_NOT_VALID : p[k - HALF]) * cx[k]; }
+    else { for (int k = 0; k < NT; k++) sum += ((LIM && y + k - HALF >= lim_row) ? HOP_NOT_VALID : p[(ptrdiff_t)(k - HALF) * stride]) * cy[k]; }
     int16_t val = (int16_t)((sum + 32) >> 6);
     if (val < 0) val = 0;
     if (val > maxVal) val = (int16_t)maxVal;
@@ -28,7 +28,7 @@ __device__ static inline int mc_sample(const int16_t* __restrict__ src, int stri
   for (int k = 0; k < NT; k++) {                              // horizontal (isFirst, !isLast) then vertical (!isFirst, isLast)
     const int16_t* q = p + (ptrdiff_t)(k - HALF) * stride;
     int sum = 0;
-    for (int j = 0; j < NT; j++) sum += q[j - HALF] * cx[j];
+    for (int j = 0; j < NT; j++) sum += ((LIM && y + k - HALF >= lim_row) ? HOP_NOT_VALID : q[j - HALF]) * cx[j];
     int16_t t = (int16_t)((sum + off1) >> shift1);
     sum2 += t * cy[k];
   }
@@ -43,6 +43,8 @@ struct PredShared { int16_t patch[128 * 130]; };
 
 // one job, one plane, on the 256 threads of the calling workgroup (a barrier inside the GT branch: uniform over the workgroup)
 // tile != nullptr: the block goes to `tile` (pitch = the block's width in this plane) instead of the prediction picture
+// ROW_LIMIT: the reads honour hop_ctx_set_row_limit (the encoder's kernels); false: the limited loops are not compiled in at all (the decoder, which sees the real state)
+template <bool ROW_LIMIT>
 __device__ static void pred_inter_body(PredShared& sh, const hop_pred_job& jb, const int comp, const hop_pics& pic, int16_t* tile = nullptr) {
   const int tid = threadIdx.x;
   const bool chroma = comp != 0;
@@ -58,11 +60,22 @@ __device__ static void pred_inter_body(PredShared& sh, const hop_pred_job& jb, c
   for (int k = 0; k < 8; k++) any = any || jb.gt[k] != 0;
   if (tile) dst = tile;
   else dst += (size_t)(by + (chroma ? jb.dst_row_off >> 1 : jb.dst_row_off)) * dpitch + bx;   // dst_row_off: the candidate slot's copy of the prediction picture
+  // hop_ctx_set_row_limit: the first row of this plane the PU must not see (the chroma limit is half the luma one); the reads reach 4 rows below the block or patch at most.
+  // Whether they reach the limit is the same for the whole workgroup, and never true while the limit is off.
+  const int lim = ROW_LIMIT ? __builtin_amdgcn_readfirstlane(hop_row_limit(pic, jb.pu_y)) : HOP_NO_ROW_LIMIT, lim_p = lim == HOP_NO_ROW_LIMIT ? lim : (chroma ? lim >> 1 : lim);
   if (!jb.use_gt || !any) {                                   // plain motion compensation, :650-678 / :1246-1289
     const int16_t* r = ref + (ptrdiff_t)(by + iy) * rstride + bx + ix;
-    for (int i = tid; i < bw * bh; i += 256) {
-      int y = i / bw, x = i - y * bw;
-      dst[(size_t)y * dpitch + x] = (int16_t)(chroma ? mc_sample<4>(r, rstride, x, y, xf, yf, bd) : mc_sample<8>(r, rstride, x, y, xf, yf, bd));
+    const int lim_r = lim_p - (by + iy);
+    if (!ROW_LIMIT || lim_r >= bh + 4) {
+      for (int i = tid; i < bw * bh; i += 256) {
+        int y = i / bw, x = i - y * bw;
+        dst[(size_t)y * dpitch + x] = (int16_t)(chroma ? mc_sample<4, false>(r, rstride, x, y, xf, yf, bd) : mc_sample<8, false>(r, rstride, x, y, xf, yf, bd));
+      }
+    } else {
+      for (int i = tid; i < bw * bh; i += 256) {
+        int y = i / bw, x = i - y * bw;
+        dst[(size_t)y * dpitch + x] = (int16_t)(chroma ? mc_sample<4, true>(r, rstride, x, y, xf, yf, bd, lim_r) : mc_sample<8, true>(r, rstride, x, y, xf, yf, bd, lim_r));
+      }
     }
     return;
   }
@@ -70,9 +83,17 @@ __device__ static void pred_inter_body(PredShared& sh, const hop_pred_job& jb, c
   const int PP = 2 * bw + 2;
   {
     const int16_t* r = ref + (ptrdiff_t)(by + iy - bh / 2) * rstride + bx + ix - bw / 2;
-    for (int i = tid; i < 4 * bw * bh; i += 256) {
-      int y = i / (2 * bw), x = i - y * (2 * bw);
-      sh.patch[y * PP + x] = (int16_t)(chroma ? mc_sample<4>(r, rstride, x, y, xf, yf, bd) : mc_sample<8>(r, rstride, x, y, xf, yf, bd));
+    const int lim_r = lim_p - (by + iy - bh / 2);
+    if (!ROW_LIMIT || lim_r >= 2 * bh + 4) {
+      for (int i = tid; i < 4 * bw * bh; i += 256) {
+        int y = i / (2 * bw), x = i - y * (2 * bw);
+        sh.patch[y * PP + x] = (int16_t)(chroma ? mc_sample<4, false>(r, rstride, x, y, xf, yf, bd) : mc_sample<8, false>(r, rstride, x, y, xf, yf, bd));
+      }
+    } else {
+      for (int i = tid; i < 4 * bw * bh; i += 256) {
+        int y = i / (2 * bw), x = i - y * (2 * bw);
+        sh.patch[y * PP + x] = (int16_t)(chroma ? mc_sample<4, true>(r, rstride, x, y, xf, yf, bd, lim_r) : mc_sample<8, true>(r, rstride, x, y, xf, yf, bd, lim_r));
+      }
     }
   }
   __syncthreads();

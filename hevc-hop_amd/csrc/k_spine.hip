@@ -21,12 +21,14 @@
 #define STASH_SAMPLES 6144          // 64 x 64 luma + 2 x 32 x 32 chroma
 #define STASH_SLOTS (16 * hopspine::SPINE_LANES)   // 16 per CTU row in flight
 
-__global__ void k_valid_pattern(const int32_t* __restrict__ q, int n, const int16_t* __restrict__ y00, int stride, uint8_t* __restrict__ out) {
+// (hop_ctx_set_row_limit: a probe row at or below the limit of the PU's CTU row holds the sentinel, whatever is there)
+__global__ void k_valid_pattern(const int32_t* __restrict__ q, int n, hop_pics pic, uint8_t* __restrict__ out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int32_t* p = q + 6 * i;
-  const int16_t* lb = y00 + (ptrdiff_t)(p[1] + (p[5] >> 2) + p[3] + 4) * stride + (p[0] + (p[4] >> 2));
-  out[i] = (lb[0] != HOP_NOT_VALID && lb[p[2] + 4] != HOP_NOT_VALID) ? 1 : 0;
+  const int row = p[1] + (p[5] >> 2) + p[3] + 4;
+  const int16_t* lb = pic.ss_y + (ptrdiff_t)row * pic.stride_y + (p[0] + (p[4] >> 2));
+  out[i] = (row < hop_row_limit(pic, p[1]) && lb[0] != HOP_NOT_VALID && lb[p[2] + 4] != HOP_NOT_VALID) ? 1 : 0;
 }
 
 // grid (n, 3): block i of plane blockIdx.y between the reconstruction picture and its stash slot; rect4 = x, y, size, slot
@@ -114,7 +116,7 @@ int hop_valid_pattern(hop_ctx* c, int n, const int32_t* xywh_mv, uint8_t* out) {
   void* st; int r = spine_stage(c, (size_t)n * 24 + 256 + n, &st); if (r) return r;
   char* b = (char*)st; const size_t o = ((size_t)n * 24 + 255) & ~(size_t)255;
   HIPCHK(c, hipMemcpyAsync(b, xywh_mv, (size_t)n * 24, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(k_valid_pattern, dim3((n + 63) / 64), dim3(64), 0, c->stream, (const int32_t*)b, n, c->ss00[0], c->stride_y, (uint8_t*)(b + o));
+  hipLaunchKernelGGL(k_valid_pattern, dim3((n + 63) / 64), dim3(64), 0, c->stream, (const int32_t*)b, n, hop_make_pics(c), (uint8_t*)(b + o));
   HIPCHK(c, hipMemcpyAsync(out, b + o, (size_t)n, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return HOP_OK;
@@ -478,6 +480,11 @@ int hop_encode_set_shard(hop_ctx* c, int rank, int world, hop_allgather_fn fn, v
   c->shard_rank = rank; c->shard_world = world; c->shard_fn = fn; c->shard_user = user;
   return HOP_OK;
 }
+int hop_encode_set_exact(hop_ctx* c, int on) {
+  if (!c) return hop_set_err(c, HOP_ERR_ARG, "hop_encode_set_exact: bad argument");
+  c->enc_exact = on ? 1 : -1;
+  return HOP_OK;
+}
 void hop_encode_stats(double ms[16], double calls[16]) { memcpy(ms, g_stat_ms, sizeof(g_stat_ms)); memcpy(calls, g_stat_calls, sizeof(g_stat_calls)); }
 
 // One picture through the RD spine on the device: the original must be resident (hop_upload_orig).  Afterwards the reconstruction picture (hop_recon_download) holds the
@@ -504,6 +511,20 @@ int hop_encode_frame(hop_ctx* c, const hop_enc_params* p, double* ctu_cost, uint
     cfg.shard_rank = c->shard_rank; cfg.shard_world = c->shard_world; cfg.shard = &comm;
   }
   if (p->wavefront_lag > 0 && p->first_ctus > 0) return hop_set_err(c, HOP_ERR_ARG, "hop_encode_frame: first_ctus applies to the raster-order mode");
+  // exact wavefront (hop_encode_set_exact, or HOP_ENCODE_EXACT=1 where that was never called): a mode of this entry only -- the kernels keep the rows below out of sight
+  // (hop_ctx_set_row_limit, on for this call), the spine waits for the rows above (EncConfig::exact).  Raster order (wavefront_lag = 0) is exact as it is.
+  bool exact = c->enc_exact > 0;
+  if (c->enc_exact == 0) { const char* e = getenv("HOP_ENCODE_EXACT"); exact = e && atoi(e) != 0; }
+  if (p->wavefront_lag <= 0) exact = false;
+  if (exact) {
+    int groups = 1; if (const char* e = getenv("HOP_SPINE_GROUPS")) groups = atoi(e);
+    if (p->streams > 1) return hop_set_err(c, HOP_ERR_ARG, "hop_encode_frame: the exact wavefront (hop_encode_set_exact) runs its rows as fibers of one pool, not on streams of their own (streams > 1)");
+    if (c->shard_world > 1) return hop_set_err(c, HOP_ERR_ARG, "hop_encode_frame: the exact wavefront (hop_encode_set_exact) does not code a sharded picture (hop_encode_set_shard)");
+    if (n_pic > 1 && groups > 1) return hop_set_err(c, HOP_ERR_ARG, "hop_encode_frame: the exact wavefront (hop_encode_set_exact) codes a stacked context as one group (HOP_SPINE_GROUPS > 1)");
+    if (p->wavefront_lag < 2) return hop_set_err(c, HOP_ERR_ARG, "hop_encode_frame: the exact wavefront (hop_encode_set_exact) needs wavefront_lag >= 2: a CTU's neighbour above and to the right must be coded");
+    cfg.exact = 1;
+  }
+  struct RowLimit { hop_ctx* c; int was; RowLimit(hop_ctx* c, bool on) : c(c), was(c->row_limit) { if (on) c->row_limit = 1; } ~RowLimit() { c->row_limit = was; } } row_limit(c, exact);   // (views are made below and inherit it)
   {                                                                      // the images of the levels (one per candidate slot) and their part of the stash
     const size_t ctus = (size_t)((c->pic_w + 63) >> 6) * ((c->pic_h + 63) >> 6), want = ctus * (c->slots + 1) * COEF_PER_CTU * 4;
     if (c->coefpic) { (void)hipFree(c->coefpic); c->coefpic = nullptr; }
@@ -597,7 +618,7 @@ int hop_encode_frame(hop_ctx* c, const hop_enc_params* p, double* ctu_cost, uint
   for (auto v : gviews) hop_ctx_destroy(v);
   for (auto b : vbe) delete b;
   for (auto v : views) { if (rc != HOP_OK && v->err[0] && !c->err[0]) strncpy(c->err, v->err, sizeof(c->err) - 1); hop_ctx_destroy(v); }
-  for (auto e : encs) { g_stat_calls[10] += (double)e->reach_below.load(); g_stat_calls[11] += (double)e->reach_above.load(); }   // the visibility check of the wavefront (hop_spine.h)
+  for (auto e : encs) { g_stat_calls[10] += (double)e->reach_below.load(); g_stat_calls[11] += (double)e->reach_above.load(); g_stat_calls[12] += (double)e->exact_waits.load(); g_stat_ms[12] += (double)e->exact_wait_ns.load() * 1e-6; }   // 10, 11: the visibility check of the wavefront (hop_spine.h); 12: the exact wavefront's waits for the row above
   g_stat_ms[10] = (double)enc.first_below.load(); g_stat_ms[11] = (double)enc.first_above.load();
   if (rc == HOP_OK) {
     const int n = enc.n_ctu();

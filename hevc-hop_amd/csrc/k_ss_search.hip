@@ -159,9 +159,10 @@ __device__ static inline void ss_tile_origin(const hop_pu_job& jb, const SsGeom&
 
 // stage the reference window of a tile (biased +1); note whether a sentinel was seen.  (x0,y0) = picture position of the
 // tile's first sample.  Rows are clamped into the allocation (margin + guard rows): a clamped row only feeds displacements
-// that lie outside every window a checked job can have.
+// that lie outside every window a checked job can have.  Rows from `lim` on (hop_row_limit of the PU or cell; HOP_NO_ROW_LIMIT: none) are staged as the sentinel
+// without being read: a test per row, the same for the whole wave.
 __device__ static inline void ss_stage_ref(uint16_t* __restrict__ tile, const hop_pics& pic, int x0, int y0, int rows, int cols, int pitch,
-                                           int wave, int lane, int* has_sentinel) {
+                                           int wave, int lane, int lim, int* has_sentinel) {
   const int ylo = -(HOP_MARGIN_Y + HOP_GUARD_ROWS) + 1, yhi = pic.pic_h + HOP_MARGIN_Y + HOP_GUARD_ROWS - 2;
   const int cw = cols >> 1;
   bool zero = false;
@@ -169,6 +170,11 @@ __device__ static inline void ss_stage_ref(uint16_t* __restrict__ tile, const ho
     const int y = min(max(y0 + r, ylo), yhi);
     const uint32_t* srow = (const uint32_t*)(pic.ss_y + (ptrdiff_t)y * pic.stride_y + x0);
     uint32_t* trow = (uint32_t*)(tile + (size_t)r * pitch);
+    if (y0 + r >= lim) {                                                   // below the row limit: the biased sentinel
+      for (int cdw = lane; cdw < cw; cdw += 64) trow[cdw] = 0;
+      zero = true;
+      continue;
+    }
     for (int cdw = lane; cdw < cw; cdw += 64) {
       uint32_t v = bias_pk(srow[cdw]);                                   // per-half +1 (v_pk_add_u16): -1 -> 0 without a carry into the neighbour
       zero = zero || ((v & 0xFFFFu) == 0) || ((v >> 16) == 0);
@@ -189,7 +195,7 @@ __device__ static inline void ss_stage_org(uint32_t* __restrict__ orgT, const ho
 }
 __device__ static inline void ss_stage(uint16_t* __restrict__ tile, uint32_t* __restrict__ orgT, const hop_pics& pic, int bx, int by, int dx0, int dy0,
                                        int rows, int cols, int pitch, int W, int hs, int step, int HS, int wave, int lane, int* has_sentinel) {
-  ss_stage_ref(tile, pic, bx + dx0, by + dy0, rows, cols, pitch, wave, lane, has_sentinel);
+  ss_stage_ref(tile, pic, bx + dx0, by + dy0, rows, cols, pitch, wave, lane, hop_row_limit(pic, by), has_sentinel);
   ss_stage_org(orgT, pic, bx, by, W, hs, step, HS, wave, lane);
 }
 
@@ -716,7 +722,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     __syncthreads();                                               // the previous tile's readers are done with LDS
     if (threadIdx.x == 0) has_sentinel = 0;
     __syncthreads();
-    ss_stage_ref(tile, pic, gx + dx0, gy + dy0, rows, cols, pitch, wave, lane, &has_sentinel);
+    ss_stage_ref(tile, pic, gx + dx0, gy + dy0, rows, cols, pitch, wave, lane, hop_row_limit(pic, gy), &has_sentinel);   // (a cell lies inside one CTU row: its families share the limit)
     for (int f = 0; f < cnt; f++) {
       const hop_pu_job* head = jobs + mem[f];
       ss_stage_org(orgT + f * fstride, pic, head->pu_x, head->pu_y, N, hs, step, HS, wave, lane);

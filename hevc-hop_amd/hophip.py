@@ -408,6 +408,16 @@ class Context:
         fn = ctypes.cast(allgather.fn, ctypes.c_void_p) if allgather is not None else None
         self._chk(self.L.hop_encode_set_shard(self.h, rank, world, fn, None), "hop_encode_set_shard")
 
+    def set_row_limit(self, on):
+        """hop_ctx_set_row_limit: the searches, predictions and validity probes read the SS reference as raster order has it -- the sentinel from the bottom of the PU's CTU row on"""
+        self.L.hop_ctx_set_row_limit.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        self._chk(self.L.hop_ctx_set_row_limit(self.h, 1 if on else 0), "hop_ctx_set_row_limit")
+
+    def set_exact(self, on):
+        """hop_encode_set_exact (sticky): encode_frame in wavefront mode takes the raster-order decisions for any wavefront_lag >= 2 -- row limit below, waits on the row above"""
+        self.L.hop_encode_set_exact.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        self._chk(self.L.hop_encode_set_exact(self.h, 1 if on else 0), "hop_encode_set_exact")
+
     def levels_download(self):
         """hop_levels_download: (n_ctu, 6144) int32 -- per CTU 4096 luma + 1024 Cb + 1024 Cr levels in the reference's TComDataCU layout"""
         n = ((self.W + 63) // 64) * ((self.sub_h + 63) // 64) * self.pictures
@@ -617,7 +627,8 @@ class Context:
         names = ("me_search", "pred_inter", "distortion", "valid_pattern", "inter_cu", "inter_cu_skip", "intra_cu", "recon_stash", "commit", "evaluation_wait")
         d = {k: {"ms": ms[i], "calls": int(calls[i])} for i, k in enumerate(names)}
         d["rendezvous"] = {"rounds": int(calls[14]), "requests": int(calls[15]), "serve_ms": float(ms[14]), "run_ms": float(ms[13]),
-                           "searches_reaching_below": int(calls[10]), "first_ctu_reaching_below": int(ms[10]), "searches_reaching_above": int(calls[11]), "first_ctu_reaching_above": int(ms[11])}
+                           "searches_reaching_below": int(calls[10]), "first_ctu_reaching_below": int(ms[10]), "searches_reaching_above": int(calls[11]), "first_ctu_reaching_above": int(ms[11]),
+                           "waits": int(calls[12]), "wait_ms": float(ms[12])}
         return d
 
     def tu_roundtrip(self, jobs, want_levels=True):

@@ -56,6 +56,25 @@ void hop_set_search_range(int pic_w, int pic_h, int cu_x, int cu_y, int cu_size,
   out[0] = lh >> 2; out[1] = rh >> 2; out[2] = lv >> 2; out[3] = rv >> 2; out[4] = off_x; out[5] = off_y;
 }
 
+// The rightmost CTU column in which hop_me_search (all stages) reads samples above row_top, the top of the PU's CTU row -- -1: it reads none there.  What it reads:
+// the search window with the block at every displacement and the validity probes 4 samples below and to its right (xPatternSearch, TEncSearch.cpp:6262-6371), the
+// 8-tap reach of the fractional refinement around the integer vector (:6564-6610), and the GT patch -- half a block around the displaced block -- around the integer
+// vector and around every AMVP start vector (:5106-5178), which need not lie inside the window.  m = half the larger block side + 8 covers the first three, as the
+// spine's visibility check counts them (CtuWorker::reach_check).
+int hop_me_reach_above(int pic_w, const hop_pu_job* job, int row_top) {
+  const int w = job->w, h = job->h, m = (w > h ? w : h) / 2 + 8;
+  int x = -1;
+  if (job->pu_y + job->rng_top - m < row_top) x = job->pu_x + job->rng_right + w + m;
+  for (int i = 0; i < job->n_amvp && i < 2; i++) {
+    const int ax = job->amvp[2 * i], ay = job->amvp[2 * i + 1];
+    if (ax == 0 && ay == 0) continue;                                      // (not a start vector, :5120)
+    const int sx = (int)(int16_t)ax >> 2, sy = (int)(int16_t)ay >> 2;
+    if (job->pu_y + sy - h / 2 < row_top) x = imax(x, job->pu_x + sx + w + w / 2);
+  }
+  if (x < 0) return -1;
+  return imin(x, pic_w - 1) >> 6;
+}
+
 uint32_t hop_component_bits(int v) { return hl_component_bits(v); }
 uint32_t hop_bits_gt(const int v[8]) {   // IT_GT_AFFINE: corners 0..2 only, TComRdCost.h:205-215
   uint32_t b = 0; for (int i = 0; i < 6; i++) b += hl_component_bits(v[i]); return b;

@@ -33,6 +33,11 @@ namespace hopspine {
 
 bool posted_requests_allowed = true;
 
+void Backend::wait_counter(std::atomic<int>* ctr, int target) { while (ctr->load() < target) std::this_thread::yield(); }
+
+// exact wavefront: the wait of a CTU for the row above was ended (a cancel request, a failure), not answered: the CTU is given up (code_row)
+struct Abandoned {};
+
 static const double MAX_DOUBLE = 1.7e+308;           // TLibCommon/CommonDef.h
 static const uint32_t MAX_UINT = 0xFFFFFFFFu;
 static const int CTU = 64;
@@ -224,6 +229,9 @@ class CtuWorker {
   void compress_cu(int d, int parent_part_size);
   void check_best_mode(int d, bool save_recon);
   void reach_check(int px, int py, int w, int h, const int* r6);
+  void wait_above(int col);
+  bool abandoned_ = false;                                                // a candidate child of this worker gave its CTU up (Abandoned): the worker follows once its children have ended
+  void fork_cands(int n, const std::function<void(int)>& fn);
   bool raster_below_ = [] { const char* e = getenv("HOP_SPINE_RASTER_BELOW"); return e ? atoi(e) != 0 : true; }();
   struct PendingSave { bool on; int d, x, y, size; } psave_ = { false, 0, 0, 0, 0 };
   void flush_save();
@@ -289,12 +297,31 @@ bool CtuWorker::valid_pattern(int px, int py, int w, int h, int mvx, int mvy) {
     if (by >= cfg.pic_h + 160) return false;
     int x = (int)bx - 80, y = (int)by - 80;
     x = x < 0 ? 0 : x >= cfg.pic_w ? cfg.pic_w - 1 : x; y = y < 0 ? 0 : y >= cfg.pic_h ? cfg.pic_h - 1 : y;
-    if (raster_below_ && y >= ctu_y_ + CTU) return false;            // the reference codes in raster order: nothing below the current CTU row exists yet, whatever a CTU row that
+    if (y < ctu_y_) wait_above(x >> 6);                              // exact wavefront: the reference has the rows above whole
+    if ((raster_below_ || cfg.exact) && y >= ctu_y_ + CTU) return false;            // the reference codes in raster order: nothing below the current CTU row exists yet, whatever a CTU row that
                                                                       // runs behind this one in the wavefront has committed there (HOP_SPINE_RASTER_BELOW=0: as the map has it)
     return E.committed[(size_t)(y >> 3) * W8 + (x >> 3)] != 0;
   };
   const long lb = (long)(py + (mvy >> 2) + h + 4) * stride + (px + (mvx >> 2));
   return probe(lb) && probe(lb + w + 4);
+}
+
+// Exact wavefront (EncConfig::exact): until the row above has retired CTU column `col`.  The rows further up are ahead of that row by the start gate (code_row), so this
+// one wait covers them.  Candidate children wait the same way (their lane is a fiber of its own).  Abandoned: the row above ended without coding that CTU.
+void CtuWorker::wait_above(int col) {
+  if (!cfg.exact || ctu_y_ == 0) return;
+  const int r = ctu_y_ / CTU, need = (col < E.wctu_ ? col : E.wctu_ - 1) + 1;
+  if (E.row_retired[r - 1].load() >= need) return;
+  const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  be->wait_counter(&E.row_gate[r - 1], need);
+  E.exact_waits.fetch_add(1);
+  E.exact_wait_ns.fetch_add((long long)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count());
+  if (E.row_retired[r - 1].load() < need) throw Abandoned();
+}
+// the candidates of a node as children of this worker (Backend::fork_join); a child that gives the CTU up ends quietly, and this worker gives it up when all have ended
+void CtuWorker::fork_cands(int n, const std::function<void(int)>& fn) {
+  be->fork_join(n, [&](int i) { try { fn(i); } catch (const Abandoned&) { abandoned_ = true; } });
+  if (abandoned_) { abandoned_ = false; throw Abandoned(); }
 }
 
 // (see Encoder::reach_below): the window of a motion search of the PU (px, py, w, h) with the range r6 of hop_set_search_range (left, right, top, bottom: integer vectors
@@ -527,9 +554,10 @@ bool CtuWorker::pred_inter_search(CuData& c, int ps, bool use_mrg) {
       int r6[6];
       hop_set_search_range(cfg.pic_w, cfg.pic_h, c.x, c.y, c.size, c.ctu_addr, E.wctu_, pred[0], pred[1], cfg.search_range, offx, offy, c.y == 0, c.x == 0, r6);
       j.rng_left = r6[0]; j.rng_right = r6[1]; j.rng_top = r6[2]; j.rng_bottom = r6[3]; j.off_x = r6[4]; j.off_y = r6[5];
-      reach_check(px, py, w, h, r6);
       j.pred_x = pred[0]; j.pred_y = pred[1]; j.lambda_cost = lam; j.n_amvp = info.n;
       for (int i = 0; i < info.n; i++) { j.amvp[2 * i] = info.cand[i][0]; j.amvp[2 * i + 1] = info.cand[i][1]; }
+      if (cfg.exact) { const int col = hop_me_reach_above(cfg.pic_w, &j, ctu_y_ + cfg.y_origin); if (col >= 0) wait_above(col); }   // the search reads the row above up to that column
+      reach_check(px, py, w, h, r6);
       j.flags = (cfg.fen ? HOP_FLAG_FEN : 0) | (cfg.hadme ? HOP_FLAG_HADME : 0);
       hop_pu_result r; memset(&r, 0, sizeof(r));
       tag_step(pu * 8 + 1);
@@ -867,7 +895,7 @@ void CtuWorker::spec_inter_phase(int d, std::vector<SpecCand>& cands) {
   if ((int)kids_.size() <= cfg.spec_slots) { const size_t k0 = kids_.size(); kids_.resize(cfg.spec_slots + 1, NULL); for (size_t k = k0; k < kids_.size(); k++) kids_[k] = new CtuWorker(E, lane_, be, true); }
   std::vector<int> slot; spec_slots_of(cands, 0, spec_level_slots(), slot);
   flush_save();                                                          // (the candidates about to run reuse the slots)
-  be->fork_join((int)cands.size(), [&](int i) { spec_run(d, cands[i], tmpl, slot[i]); });
+  fork_cands((int)cands.size(), [&](int i) { spec_run(d, cands[i], tmpl, slot[i]); });
 }
 
 // The candidates of the CU in temp_[d] (initialised, init_est): xCheckRDCostMerge2Nx2N's passes, then xCheckRDCostInter for 2Nx2N, Nx2N and 2NxN (the order of xCompressCU
@@ -932,7 +960,7 @@ void CtuWorker::check_merge_and_inter_spec(int d) {
     std::vector<std::vector<int> > slot(sets.size()); std::vector<int> first(sets.size() + 1, 0);
     for (size_t q = 0; q < sets.size(); q++) { spec_slots_of(sets[q]->cands, (int)q * L, L, slot[q]); first[q + 1] = first[q] + (int)sets[q]->cands.size(); }
     flush_save();                                                          // (the candidates about to run reuse the slots)
-    be->fork_join(first[sets.size()], [&](int i) {                        // (this worker waits in fork_join while its kids read the templates temp_[depth])
+    fork_cands(first[sets.size()], [&](int i) {                           // (this worker waits in fork_join while its kids read the templates temp_[depth])
       size_t q = 0; while (i >= first[q + 1]) q++;
       spec_run(depth[q], sets[q]->cands[i - first[q]], *temp_[depth[q]], slot[q][i - first[q]]);
     });
@@ -1143,6 +1171,9 @@ Encoder::Encoder(const EncConfig& cfg, Backend* be) : trace(NULL), n_candidates(
   pic.resize((size_t)n_ctu() * 256); ctu_entry.resize(n_ctu()); ctu_exit.resize(n_ctu()); committed.assign((size_t)(cfg.pic_w >> 3) * (cfg.pic_h >> 3), 0);
   for (size_t i = 0; i < pic.size(); i++) part_init(pic[i], 0);
   reach_below.store(0); reach_above.store(0); first_below.store(-1); first_above.store(-1);
+  row_retired.reset(new std::atomic<int>[hctu_]); row_gate.reset(new std::atomic<int>[hctu_]); lane_rows.reset(new std::atomic<int>[hctu_]);
+  for (int r = 0; r < hctu_; r++) { row_retired[r].store(0); row_gate[r].store(0); lane_rows[r].store(0); }
+  exact_waits.store(0); exact_wait_ns.store(0);
 }
 
 LogBackend::LogBackend(Backend* inner, const char* path) : in_(inner), f_(fopen(path, "wb")) {}
@@ -1557,7 +1588,7 @@ class FiberPool : public Backend {
 // several ranks (world > 1): this rank's rows only count their CTUs; the exchange fiber moves steps_complete on once the other ranks' CTUs of the step have arrived.
 struct WavefrontSteps {
   WavefrontSteps(int rows, int cols, int lag, int n_pic, int world, int rank)
-      : rows(rows), cols(cols), lag(lag), n_steps(cols + lag * (rows - 1)), world(world), rank(rank), in_step(n_steps, 0), finished(n_steps), steps_complete(-1), agreed_cancel(0), sync_((size_t)rows * n_pic) {
+      : rows(rows), cols(cols), lag(lag), n_steps(cols + lag * (rows - 1)), world(world), rank(rank), rif((cols + lag - 1) / lag + 1), in_step(n_steps, 0), finished(n_steps), steps_complete(-1), agreed_cancel(0), failed(false), sync_((size_t)rows * n_pic) {
     for (int r = 0; r < rows; r++) if (owned(r)) for (int c = 0; c < cols; c++) in_step[step_of(r, c)] += n_pic;
     for (auto& a : finished) a.store(0);
   }
@@ -1571,12 +1602,14 @@ struct WavefrontSteps {
   Coder load_sync(int p, int r) { std::lock_guard<std::mutex> g(m_); Coder k = sync_[(size_t)p * rows + r - 1]; coder_set_frac(k, 0); return k; }
   // rows that are threads: sleep until every step <= `step` is finished; the first failure ends everybody's wait
   void wait(int step) { std::unique_lock<std::mutex> lk(m_); cv_.wait(lk, [&] { return steps_complete.load() >= step || error; }); if (error) throw 1; }
-  void fail(std::exception_ptr e) { std::lock_guard<std::mutex> g(m_); if (!error) error = e; cv_.notify_all(); }
+  void fail(std::exception_ptr e) { std::lock_guard<std::mutex> g(m_); if (!error) error = e; failed.store(true); cv_.notify_all(); }
   const int rows, cols, lag, n_steps, world, rank;
+  const int rif;                                                        // rows of one picture that can be in flight together (+ 1 spare): row r works on lane r % rif
   std::vector<int> in_step;                                             // CTUs (of this rank) per step
   std::vector<std::atomic<int> > finished;                              // ... and how many of them are done (sharded: the exchange fiber waits on it)
   std::atomic<int> steps_complete;                                      // all steps <= this one are finished
   std::atomic<int> agreed_cancel;                                       // sharded: a cancel request every rank has seen (set after an exchange)
+  std::atomic<bool> failed;                                             // a row has failed (what the rows of the exact wavefront look at: they do not wait on steps)
   std::exception_ptr error;                                             // what the first failing row threw
  private:
   void advance() {                                                      // (lock held)
@@ -1591,33 +1624,67 @@ struct WavefrontSteps {
 
 // Row r of picture p, CTU by CTU as its steps come up, through `be`.  wait_step(s) returns once every step <= s is finished (and throws when the wavefront has failed);
 // flush, if any, runs after every CTU before it counts.  Honours hop_encode_cancel, counts hop_encode_progress; whatever ends the row early, the rows below are released.
+//
+// Exact wavefront (EncConfig::exact): no steps.  A CTU that waits for a column of the row above `lag` or more ahead would wait for a later step, which cannot start before
+// the waiting CTU ends; so the rows are gated on each other's progress instead: row r starts CTU c once row r - 1 has retired CTU min(c + lag - 1, cols - 1)
+// (Encoder::row_retired), and `lag` is the least distance between two rows.  No deadlock: row 0 never waits, neither at the gate nor inside a CTU (CtuWorker::wait_above
+// returns at once in the first row); row r > 0 waits for row r - 1 only, never for a row below it or for itself; and every wait is for a CTU row r - 1 reaches by coding
+// on, or is ended when that row ends (row_gate = ROW_ENDED).  By induction over r every row ends.  Any lag >= 2 is valid: what a CTU needs of the row above without
+// asking -- the neighbouring CTU above and to the right -- is retired at the gate.  A CTU whose wait was ended, not answered (the row above stopped: hop_encode_cancel,
+// a failure), is abandoned: it is not counted as retired, its cost, bits and distortion stay 0, and its row ends.
+// Lanes: row r works on lane r % rif (its stash slots and levels), rif = ceil(cols / lag) + 1.  Under the steps row r + rif starts after row r's last step; the progress
+// gate promises less -- row q starts CTU c once row q - 1 has RETIRED c + lag CTUs, which row q - 1 may have done long before it is let on by row q - 2, so over k rows only
+// k (lag - 1) + 1 + c retired CTUs are certain, not k lag + c -- and a row could meet the row rif above it on its lane.  So row r first waits until row r - rif has ENDED
+// (row_gate = ROW_ENDED, stored after that row's last use of the lane).  That is again a wait for a row above, which ends by the induction above, so the no-deadlock
+// argument stands; Encoder::lane_rows counts the rows on a lane and a second one is an error, not a silent overwrite.  A failure anywhere ends every row at its next gate.
 static void code_row(Encoder& E, int p, int r, int lane, Backend* be, WavefrontSteps& ws, const Coder& init, const std::function<void(int)>& wait_step, const std::function<void()>& flush, uint64_t& n_cand) {
   const EncConfig& cfg = E.config();
   CtuWorker* w = NULL;
   std::exception_ptr err;
   int c = 0;
+  const bool exact = cfg.exact != 0;
+  bool on_lane = false;
   try {
+    if (exact) {
+      if (r >= ws.rif) be->wait_counter(&E.row_gate[r - ws.rif], Encoder::ROW_ENDED);   // the row that had this lane before is done with it
+      if (E.lane_rows[r % ws.rif].fetch_add(1) != 0) { E.lane_rows[r % ws.rif].fetch_sub(1); throw 1; }
+      on_lane = true;
+    }
     w = new CtuWorker(E, lane, be);
     Coder k = init;
     for (; c < ws.cols; c++) {
       const int st = ws.step_of(r, c);
-      wait_step(st - 1);
+      if (!exact) wait_step(st - 1);
+      else {
+        if (r > 0) {
+          const int need = std::min(c + ws.lag - 1, ws.cols - 1) + 1;
+          be->wait_counter(&E.row_gate[r - 1], need);
+          if (E.row_retired[r - 1].load() < need) break;                // the row above has ended without that CTU: this row ends too
+        }
+        if (ws.failed.load()) break;                                    // a row has failed (any row: the rows above it do not wait for it and would code on)
+      }
       if (ws.world > 1 ? ws.agreed_cancel.load() != 0 : (cfg.cancel && cfg.cancel->load())) break;   // hop_encode_cancel: this row stops here
       if (c == 0 && r > 0 && ws.cols >= 2) k = ws.load_sync(p, r);
       const int a = r * ws.cols + c;
       E.ctu_entry[a] = k;
-      Coder next; w->compress_ctu(a, k, next);
+      Coder next;
+      try { w->compress_ctu(a, k, next); }
+      catch (const Abandoned&) { E.ctu_trace[a].clear(); break; }       // (exact wavefront) given up: not retired, its results stay 0
       k = next;
       if (flush) flush();                                               // (posted stash / restore / commit requests of the CTU: done before it counts)
       if (cfg.progress) cfg.progress->fetch_add(1);
       if (c == 1) ws.store_sync(p, r, k);
       if (ws.world > 1) E.ctu_exit[a] = k;                              // (travels to the other ranks)
-      ws.finish(st);
+      if (exact) { E.row_retired[r].fetch_add(1); E.row_gate[r].fetch_add(1); }
+      else ws.finish(st);
     }
-  } catch (...) { err = std::current_exception(); ws.fail(err); }      // (before the rows below are released: they then start nothing)
-  ws.abandon(r, c);
+  } catch (...) { err = std::current_exception(); ws.fail(err); }      // (before the rows below are released: under the steps they then start nothing; in exact mode they
+                                                                        // are released by ROW_ENDED below and end at the row_retired / ws.failed checks of their gate)
   if (w) n_cand = w->n_cand_;
-  delete w;
+  delete w; w = NULL;
+  if (on_lane) E.lane_rows[r % ws.rif].fetch_sub(1);                    // (before ROW_ENDED: the row rif below takes the lane after it)
+  if (exact) E.row_gate[r].store(Encoder::ROW_ENDED);
+  ws.abandon(r, c);
   if (err) std::rethrow_exception(err);
 }
 }  // namespace
@@ -1644,11 +1711,14 @@ void Encoder::wavefront_many(Encoder* const* encs, int n_pic, BatchInner* inner,
     Encoder& E = *encs[p];
     for (size_t i = 0; i < E.pic.size(); i++) part_init(E.pic[i], 0);
     std::fill(E.committed.begin(), E.committed.end(), (uint8_t)0);
+    for (int r = 0; r < rows; r++) { E.row_retired[r].store(0); E.row_gate[r].store(0); E.lane_rows[r].store(0); }
+    E.exact_waits.store(0); E.exact_wait_ns.store(0);
   }
   // one picture's rows dealt to several ranks (EncConfig::shard; the batching form only): this process runs the rows r % world == rank and a fiber that, after every
   // wavefront step, exchanges the step's finished CTUs with the other ranks
   const int world = (inner && E0.cfg_.shard_world > 1 && E0.cfg_.shard) ? E0.cfg_.shard_world : 1, rank = world > 1 ? E0.cfg_.shard_rank : 0;
   if (world > 1 && (n_pic != 1 || rank < 0 || rank >= world)) throw 1;
+  if (E0.cfg_.exact && (world > 1 || (lag < 2 && cols > 1))) throw 1;                 // (exact wavefront: one process, rows at least two CTUs apart)
   WavefrontSteps ws(rows, cols, lag, n_pic, world, rank);
   auto lane_of = [&](int p, int r) { return lane_base + p * lanes_per_pic + r % rif; };
   std::vector<uint64_t> cand((size_t)rows * n_pic, 0);

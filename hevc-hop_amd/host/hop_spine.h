@@ -7,6 +7,7 @@
 #include <stdint.h>
 #include <atomic>
 #include <functional>
+#include <memory>
 #include <stdio.h>
 #include <string>
 #include <vector>
@@ -44,6 +45,10 @@ struct EncConfig {
   // the next step's CTUs find their neighbours, search windows and contexts as in a single process.  shard_world <= 1: off.  A cancel request is agreed on through the same
   // exchange, so that all ranks leave the wavefront at the same step.
   int shard_rank, shard_world; struct ShardComm* shard;
+  // Exact wavefront (default 0; set by the device entry only, whose kernels keep the rows below out of sight: hop_ctx_set_row_limit): the rows are gated on per-row progress
+  // -- row r starts CTU c once row r - 1 has retired CTU min(c + lag - 1, columns - 1) -- instead of common steps, and a request that would read samples of the row above
+  // at a column that row has not retired yet (a motion search's window, a validity probe) waits until it has.  The decisions are then the raster-order ones for any lag >= 2.
+  int exact;
   // derived by finish_config()
   double lambda, sqrt_lambda, lambda_rdoq[3], dist_weight[2];
   uint32_t lambda_sad;
@@ -128,6 +133,8 @@ class Backend {
   // fn(0) ... fn(n - 1), each issuing requests of its own: a backend that batches runs them side by side (their requests then meet in the batches), the others one
   // after the other -- the answers, and so the results, are the same
   virtual void fork_join(int n, const std::function<void(int)>& fn) { for (int i = 0; i < n; i++) fn(i); }
+  // until *ctr >= target, counted up by another lane (a CTU row waiting for the row above).  A backend whose lanes are fibers switches to another one; here: the lanes are threads
+  virtual void wait_counter(std::atomic<int>* ctr, int target);
 };
 
 // The n-forms a backend may offer so that requests of several CTUs in flight are served by one launch chain.  The defaults loop over the single forms.
@@ -227,6 +234,13 @@ class Encoder {
   std::atomic<long> reach_below, reach_above; std::atomic<int> first_below, first_above;
   double batch_run_s = 0;                            // ... the wall time of the whole wavefront (rows' host work + serving)
   double batch_serve_s = 0;                          // ... and the wall time spent serving them (one thread; the rows' own host work runs between the rounds)
+  // exact wavefront (EncConfig::exact), per CTU row: row_retired -- the CTUs of the row whose compressCU has returned; row_gate -- what waiters watch: the same number, and
+  // ROW_ENDED once the row codes nothing more (its end, a cancel request, a failure), so that nobody waits for a CTU that never comes.  A waiter that wakes up looks at
+  // row_retired: if the CTU it waited for is not there, its wait was ended, not answered
+  enum { ROW_ENDED = 1 << 30 };
+  std::unique_ptr<std::atomic<int>[]> row_retired, row_gate;
+  std::unique_ptr<std::atomic<int>[]> lane_rows;     // ... and per lane of the picture (row r works on lane r % rif, code_row): the rows on it, never more than one
+  std::atomic<long> exact_waits; std::atomic<long long> exact_wait_ns;   // requests that waited for the row above, and the time their lanes spent waiting
  private:
   friend class CtuWorker;
   EncConfig cfg_; Backend* be_; int wctu_, hctu_;

@@ -130,6 +130,13 @@ int hop_set_fused_leaf(hop_ctx* ctx, int max_tus);
  * of all of them, each exactly as in a context of its own.  sub_h = sub_pitch = 0 returns to one picture. */
 int hop_stack_pitch(int sub_h);
 int hop_ctx_set_stack(hop_ctx* ctx, int sub_h, int sub_pitch);
+/* Raster-order visibility (no counterpart in the reference, which codes its CTUs in raster order and therefore never finds a coded sample below the CTU row it works in,
+ * TEncSlice::compressSlice TEncSlice.cpp:1000-1196): while on, every read of the SS reference by hop_me_search (all stages), hop_pred_inter / hop_pred_cost and
+ * hop_valid_pattern -- and their *_device forms -- returns the sentinel (-1) for a sample whose picture row lies at or below the bottom of the CTU row that holds the PU's
+ * top-left sample, margin samples that replicate such a row included; the chroma limit is half the luma one.  In a stacked context the rows are counted from the origin of
+ * the PU's own picture.  The resident samples are not changed; a PU in a picture's last CTU row sees everything.  Default off; views inherit the state of their parent at
+ * creation; hop_decode_frame ignores it (a decoder sees the SS reference as it is).  hop_encode_frame's exact mode (hop_encode_set_exact) switches it on for the call. */
+int hop_ctx_set_row_limit(hop_ctx* ctx, int on);
 
 /* ---- picture residency ---- */
 /* replaces: the host copy of the original into TComPic (TLibEncoder/TEncTop.cpp:363-368) */
@@ -153,6 +160,10 @@ void hop_set_search_range(int pic_w, int pic_h, int cu_x, int cu_y, int cu_size,
                           int pred_x, int pred_y, int search_range, int off_x, int off_y, int first_row, int first_col, int out[6]);
 /* replaces: TComRdCost::xGetComponentBits / getBitsGT (TLibCommon/TComRdCost.cpp:270-284, TComRdCost.h:205-215) */
 uint32_t hop_component_bits(int v);
+/* The rightmost CTU column in which hop_me_search reads samples above row_top (the first row of the PU's CTU row, in the coordinates of the job), -1 if it reads none
+ * there: the search window with block and validity probes, the fractional refinement's taps and the GT patches around the integer vector and every AMVP start vector.
+ * What a row of hop_encode_frame's exact wavefront (hop_encode_set_exact) waits for before the search: the row above must have retired that column. */
+int hop_me_reach_above(int pic_w, const hop_pu_job* job, int row_top);
 uint32_t hop_bits_gt(const int v[8]);
 /* replaces: the bits/cost bookkeeping at the tail of xMotionEstimation (TEncSearch.cpp:4654-4682):
  * folds one hop_pu_result into (mv quarter-pel, bits, cost); bits_in = ruiBits on entry. */
@@ -652,7 +663,8 @@ typedef struct {
   int32_t wavefront_lag;  /* > 0 (implies wpp): the CTU rows run as a wavefront -- row r codes CTU c once row r - 1 has finished CTU c + lag - 1 -- and the candidate
                              evaluations of all rows in flight are batched into common launches.  A wavefront is not raster order: a search sees the rows above coded up to column c + lag - 1
                              only and the rows below already coded up to c - lag - 1; with predictors of ordinary length 5 is enough (every golden picture), on the 7728x5368 frame
-                             5 and 6 leave the reference's decisions at CTU 3079, 8 nowhere in the whole frame; lag >= the picture's width in CTUs is raster order */
+                             5 and 6 leave the reference's decisions at CTU 3079, 8 nowhere in the whole frame; lag >= the picture's width in CTUs is raster order.
+                             With hop_encode_set_exact the caveat is gone: any lag >= 2 gives the raster-order decisions, and the lag is the least distance between two rows */
   int32_t plain_intra;    /* 1: the plain HM intra configurations (cfg/encoder_intra_main.cfg, encoder_intra_main10.cfg): an I slice without SS / GT search, at the context's
                              bit depth (8 or 10); 0: the HOP configuration (8 bit only: the GT warp clips to 255, TComPrediction.cpp:969) */
   int32_t streams;        /* wavefront mode: > 1 = that many views of the context (hop_ctx_create_view), one per CTU row in flight, each row's requests on its own stream so
@@ -686,8 +698,19 @@ int hop_encode_cancel(hop_ctx* ctx);
  * world = 1 (fn may be NULL) switches it off again. */
 typedef int (*hop_allgather_fn)(void* user, const void* send, void* recv, size_t bytes_per_rank);
 int hop_encode_set_shard(hop_ctx* ctx, int rank, int world, hop_allgather_fn fn, void* user);
+/* Exact wavefront: sticky, like hop_encode_set_shard.  While on, hop_encode_frame in wavefront mode takes the raster-order decisions for ANY
+ * wavefront_lag >= 2 and any content: (rows below) the searches run under hop_ctx_set_row_limit, which the call sets on the context and its views and restores afterwards;
+ * (rows above) a motion search whose window reaches above its CTU row, or a validity probe that lands there, waits until the row above has retired the CTU column it
+ * reads.  The rows are then gated on per-row progress instead of common steps: row r starts CTU c once row r - 1 has retired CTU min(c + lag - 1, columns - 1), so
+ * wavefront_lag is the minimum distance between rows.  HOP_ENCODE_EXACT=1 in the environment turns the mode on for contexts on which this has never been called.
+ * Supported: one picture, or a stacked context coded as one group.  HOP_ERR_ARG with a message: streams > 1, a sharded context, HOP_SPINE_GROUPS > 1, wavefront_lag < 2
+ * (but raster order, wavefront_lag = 0, ignores the switch).  hop_encode_cancel and a failure release the waiting rows; a CTU whose wait ended that way is abandoned: not
+ * counted by hop_encode_progress, cost, bits and distortion 0. */
+int hop_encode_set_exact(hop_ctx* ctx, int on);
 /* diagnostics of the last hop_encode_frame of this process: host wall time (ms) and number of requests per kind -- 0 ME chain, 1 predictor, 2 distortion, 3 validity
- * probes, 4 SS/GT candidates with residual, 5 without, 6 intra candidates, 7 reconstruction stash, 8 SS-reference commits */
+ * probes, 4 SS/GT candidates with residual, 5 without, 6 intra candidates, 7 reconstruction stash, 8 SS-reference commits; calls[10] / calls[11]: motion searches whose
+ * window reached coded samples below / uncoded samples above their CTU row (exact mode: the former are the searches the row limit protected, the latter must be 0);
+ * slot 12 (exact mode): calls = requests that waited for the row above, ms = the time their fibers spent waiting */
 void hop_encode_stats(double ms[16], double calls[16]);
 
 /* ---- after the search: the loop filter over the resident reconstruction ---- */
