@@ -6,6 +6,9 @@
 // intra_pred_chroma_body (k_intra_dev.inl), pred_inter_body (k_pred_dev.inl), turd_inverse_body / turd_inverse_small_body (k_turd_dev.inl), commit_plane
 // (k_ssref_dev.inl).  Every launch holds the CTUs of one level of the host's schedule (host/hop_decode.cpp); the dependencies are kept by stream order alone
 // (no spin-waits, no persistent kernel), so malformed input cannot hang the device.
+// hop_decode_stack: the same kernel over the pictures of a stacked context (hop_ctx_set_stack) -- what the reference does by running TDecTop::decode once per view.  A
+// level's launch holds that level's CTUs of every picture; a CTU addresses the planes by the rows of the stack and reasons about edges (intra availability, clipMv, the
+// margins the commit extends) in the rows of its own picture.  hop_decode_frame is the one-picture case.
 #include <string.h>
 #include <vector>
 #include "hop_dev.h"
@@ -14,7 +17,8 @@
 #include "k_pred_dev.inl"
 #include "k_ssref_dev.inl"
 
-extern "C" int hop_dec_plan(int pic_w, int pic_h, int allow_inter, const hop_cu_part* parts, int schedule, int32_t* ctu_level, int32_t* n_levels, char* err, size_t errn);
+extern "C" int hop_dec_plan_stack(int pic_w, int sub_h, int n_pic, int allow_inter, const hop_cu_part* parts, int schedule, int32_t* ctu_level, int32_t* n_levels,
+                                  const char* noun, char* err, size_t errn);   // host/hop_decode.cpp
 
 namespace {
 
@@ -38,27 +42,28 @@ __device__ inline void dec_zpos(int z, int& x4, int& y4) {
   for (int b = 0; b < 4; b++) { x4 |= ((z >> (2 * b)) & 1) << b; y4 |= ((z >> (2 * b + 1)) & 1) << b; }
 }
 // availability of the neighbour units of a block (TComDataCU::getPUAboveRightAdi / getPUBelowLeftAdi in z-order; what the encoder's spine computes, hop_spine.cpp)
-__device__ inline bool dec_ar_avail(int x, int y, int k, int pic_w) {
+// Rows are absolute (a stack's picture k starts at row top = k * sub_pitch, a multiple of 64): "above the picture" is y == top, "below it" y >= bottom = top + sub_h.
+__device__ inline bool dec_ar_avail(int x, int y, int k, int pic_w, int top) {
   if (x + 4 * k >= pic_w) return false;
-  if (((x & 63) >> 2) + k < 16) return (y & 63) ? dec_zpix(x, y) > dec_zpix(x + 4 * k, y - 4) : y > 0;
-  return (y & 63) ? false : y > 0;
+  if (((x & 63) >> 2) + k < 16) return (y & 63) ? dec_zpix(x, y) > dec_zpix(x + 4 * k, y - 4) : y > top;
+  return (y & 63) ? false : y > top;
 }
-__device__ inline bool dec_bl_avail(int x, int y, int k, int pic_h) {
-  if (y + 4 * k >= pic_h) return false;
+__device__ inline bool dec_bl_avail(int x, int y, int k, int bottom) {
+  if (y + 4 * k >= bottom) return false;
   if (((y & 63) >> 2) + k < 16) return (x & 63) ? dec_zpix(x, y) > dec_zpix(x - 4, y + 4 * k) : x > 0;
   return false;
 }
 // the intra job of a luma block at (x, y) of `size` luma samples (chroma: the same flags, per 2-sample unit), filled by the workgroup; ends with a barrier
-__device__ void dec_intra_job(hop_intra_job& j, int x, int y, int size, int pic_w, int pic_h) {
+__device__ void dec_intra_job(hop_intra_job& j, int x, int y, int size, int pic_w, int top, int bottom) {
   const int tid = threadIdx.x, u = size / 4;
   if (tid == 0) { j.x = x; j.y = y; j.strong = 1; }                  // SPS strong_intra_smoothing of both configurations
   if (tid < 4 * u + 1) {
     bool a;
-    if (tid == 2 * u) a = (x & 63) ? ((y & 63) ? true : y > 0) : ((y & 63) ? x > 0 : (x > 0 && y > 0));
-    else if (tid > 3 * u) a = dec_ar_avail(x + size - 4, y, tid - 3 * u, pic_w);
-    else if (tid > 2 * u) a = y > 0;
+    if (tid == 2 * u) a = (x & 63) ? ((y & 63) ? true : y > top) : ((y & 63) ? x > 0 : (x > 0 && y > top));
+    else if (tid > 3 * u) a = dec_ar_avail(x + size - 4, y, tid - 3 * u, pic_w, top);
+    else if (tid > 2 * u) a = y > top;
     else if (tid >= u) a = x > 0;
-    else a = dec_bl_avail(x, y + size - 4, u - tid, pic_h);
+    else a = dec_bl_avail(x, y + size - 4, u - tid, bottom);
     j.flags[tid] = a ? 1 : 0;
   }
   __syncthreads();
@@ -71,7 +76,9 @@ struct DecArgs {
   int16_t* rec[3]; int16_t* ss00[3];
   int wctu, qp_scaled[3];
   int commit;                                  // an ISS slice commits every CU to the SS reference; an I slice has none
+  int n_ctu, sub_h, sub_pitch;                 // the stack: CTUs and rows of one picture, the pictures' origins sub_pitch rows apart (0: one picture of sub_h rows)
 };
+struct DecPic { int top, bottom; };            // the first row of the CTU's picture and the first row below it, in the rows of the stack
 
 // one TU of one plane: reconstruction = clip(prediction + inverse residual), or the prediction for cbf 0.  (x, y) in luma samples, log2 in this plane's samples
 __device__ void dec_tu(DecShared& sh, const DecArgs& A, int comp, int x, int y, int log2, bool cbf, bool tskip, bool dst, const int32_t* lv) {
@@ -99,14 +106,14 @@ __device__ void dec_tu(DecShared& sh, const DecArgs& A, int comp, int x, int y, 
 }
 
 // xReconIntraQT: the luma TUs in z-order (predicted from the reconstruction, DST for 4x4), then the chroma TUs (the 4x4 chroma of four 4x4 luma TUs with the first)
-__device__ void dec_intra_cu(DecShared& sh, const DecArgs& A, const hop_cu_part* P, const int32_t* LV, int z, int cx, int cy, int log2cu) {
+__device__ void dec_intra_cu(DecShared& sh, const DecArgs& A, DecPic pp, const hop_cu_part* P, const int32_t* LV, int z, int cx, int cy, int log2cu) {
   const int np = 1 << (2 * (log2cu - 2));
   for (int u = 0; u < np;) {
     const hop_cu_part& q = P[z + u];
     const int l2 = log2cu - q.tr_idx, tn = 1 << (2 * (l2 - 2));
     int x4, y4; dec_zpos(z + u, x4, y4);
     const int x = (cx & ~63) + 4 * x4, y = (cy & ~63) + 4 * y4, N = 1 << l2;
-    dec_intra_job(sh.ij, x, y, N, A.pic.pic_w, A.pic.pic_h);
+    dec_intra_job(sh.ij, x, y, N, A.pic.pic_w, pp.top, pp.bottom);
     if (threadIdx.x == 0) sh.ij.size = N;
     __syncthreads();
     intra_pred_body(sh.u.in, &sh.ij, q.luma_dir, A.pic, A.rec[0]);
@@ -123,7 +130,7 @@ __device__ void dec_intra_cu(DecShared& sh, const DecArgs& A, const hop_cu_part*
     if (l2 == 2) { tn = 4; lc = 2; bit = q.tr_idx - 1; }               // chroma of the parent 8x8 node, with its first 4x4 block (TDecCu.cpp:605-610)
     int x4, y4; dec_zpos(z + u, x4, y4);
     const int x = (cx & ~63) + 4 * x4, y = (cy & ~63) + 4 * y4, Nc = 1 << lc;
-    dec_intra_job(sh.ij, x, y, 2 * Nc, A.pic.pic_w, A.pic.pic_h);
+    dec_intra_job(sh.ij, x, y, 2 * Nc, A.pic.pic_w, pp.top, pp.bottom);
     if (threadIdx.x == 0) sh.ij.size = Nc;
     __syncthreads();
     for (int comp = 1; comp < 3; comp++) {
@@ -150,16 +157,17 @@ __device__ void dec_pu_rect(int ps, int S, int pu, int& ox, int& oy, int& w, int
 }
 
 // xReconInter: every PU predicted from the SS reference, then the residual quadtree added TU by TU (a skip CU or root cbf 0: the prediction)
-__device__ void dec_inter_cu(DecShared& sh, const DecArgs& A, const hop_cu_part* P, const int32_t* LV, int z, int cx, int cy, int log2cu) {
+__device__ void dec_inter_cu(DecShared& sh, const DecArgs& A, DecPic pp, const hop_cu_part* P, const int32_t* LV, int z, int cx, int cy, int log2cu) {
   const int S = 1 << log2cu, ps = P[z].part_size, npu = ps == 0 ? 1 : ps == 3 ? 4 : 2;
-  const int pic_w = A.pic.pic_w, pic_h = A.pic.pic_h;
+  const int pic_w = A.pic.pic_w;
   for (int pu = 0; pu < npu; pu++) {
     if (threadIdx.x == 0) {
       int ox, oy, w, h; dec_pu_rect(ps, S, pu, ox, oy, w, h);
       const hop_cu_part& p = P[dec_zpix(cx + ox, cy + oy)];
       hop_pred_job j; memset(&j, 0, sizeof(j));
       j.pu_x = cx + ox; j.pu_y = cy + oy; j.w = w; j.h = h;
-      const int hmax = (pic_w + 8 - cx - 1) * 4, hmin = (-64 - 8 - cx + 1) * 4, vmax = (pic_h + 8 - cy - 1) * 4, vmin = (-64 - 8 - cy + 1) * 4;   // clipMv at the CU
+      const int hmax = (pic_w + 8 - cx - 1) * 4, hmin = (-64 - 8 - cx + 1) * 4;                                     // clipMv at the CU, against its own picture
+      const int vmax = (pp.bottom + 8 - cy - 1) * 4, vmin = (pp.top - 64 - 8 - cy + 1) * 4;
       j.mv_x = min(hmax, max(hmin, (int)p.mv[0])); j.mv_y = min(vmax, max(vmin, (int)p.mv[1]));
       j.use_gt = (!p.merge_flag && p.gt_flag) ? 1 : 0;
       for (int k = 0; k < 8; k++) j.gt[k] = p.gt[k];
@@ -187,51 +195,62 @@ __device__ void dec_inter_cu(DecShared& sh, const DecArgs& A, const hop_cu_part*
 
 __global__ __launch_bounds__(256) void k_dec_ctu(DecArgs A) {
   __shared__ DecShared sh;
-  const int ctu = A.order[blockIdx.x];
-  const int cx0 = (ctu % A.wctu) * 64, cy0 = (ctu / A.wctu) * 64;
+  const int ctu = A.order[blockIdx.x];                                 // picture * n_ctu + the CTU's raster address in its picture
+  const int k = ctu / A.n_ctu, a = ctu - k * A.n_ctu;
+  const DecPic pp = { k * A.sub_pitch, k * A.sub_pitch + A.sub_h };
+  const int cx0 = (a % A.wctu) * 64, cy0 = pp.top + (a / A.wctu) * 64;  // addressing stays absolute: rows of the stack
   const hop_cu_part* P = A.parts + (size_t)ctu * 256;
   const int32_t* LV = A.levels + (size_t)ctu * 6144;
-  const int pw = A.pic.pic_w, ph = A.pic.pic_h;
+  const int pw = A.pic.pic_w, ph = A.sub_h, sp = A.sub_pitch;
   for (int z = 0; z < 256;) {
     const int mode = P[z].pred_mode;
     if (mode != 0 && mode != 1) { z++; continue; }                     // MODE_NONE: outside the picture
     const int log2cu = 6 - P[z].depth;
     int x4, y4; dec_zpos(z, x4, y4);
     const int cx = cx0 + 4 * x4, cy = cy0 + 4 * y4, S = 1 << log2cu;
-    if (mode == 1) dec_intra_cu(sh, A, P, LV, z, cx, cy, log2cu);
-    else dec_inter_cu(sh, A, P, LV, z, cx, cy, log2cu);
+    if (mode == 1) dec_intra_cu(sh, A, pp, P, LV, z, cx, cy, log2cu);
+    else dec_inter_cu(sh, A, pp, P, LV, z, cx, cy, log2cu);
     z += 1 << (2 * (log2cu - 2));                                      // the units of the CU
     if (!A.commit) { __syncthreads(); continue; }
     // xFindSSRef2Copy: the CU into the SS reference, its halo re-extended
-    commit_plane<false>(A.ss00[0], A.pic.stride_y, pw, ph, 0, HOP_MARGIN_Y, cx, cy, S, A.rec[0], pw);
+    commit_plane<false>(A.ss00[0], A.pic.stride_y, pw, ph, sp, HOP_MARGIN_Y, cx, cy, S, A.rec[0], pw);
     __syncthreads();
-    commit_plane<false>(A.ss00[1], A.pic.stride_c, pw >> 1, ph >> 1, 0, HOP_MARGIN_C, cx >> 1, cy >> 1, S >> 1, A.rec[1], pw >> 1);
+    commit_plane<false>(A.ss00[1], A.pic.stride_c, pw >> 1, ph >> 1, sp >> 1, HOP_MARGIN_C, cx >> 1, cy >> 1, S >> 1, A.rec[1], pw >> 1);
     __syncthreads();
-    commit_plane<false>(A.ss00[2], A.pic.stride_c, pw >> 1, ph >> 1, 0, HOP_MARGIN_C, cx >> 1, cy >> 1, S >> 1, A.rec[2], pw >> 1);
+    commit_plane<false>(A.ss00[2], A.pic.stride_c, pw >> 1, ph >> 1, sp >> 1, HOP_MARGIN_C, cx >> 1, cy >> 1, S >> 1, A.rec[2], pw >> 1);
     __syncthreads();
   }
 }
 
 }  // namespace
 
-extern "C" int hop_decode_frame(hop_ctx* c, const hop_dec_params* p, const hop_cu_part* parts, const int32_t* levels) {
-  if (!c || !p || !parts || !levels) return hop_set_err(c, HOP_ERR_ARG, "hop_decode_frame: bad argument");
-  if (c->sub_pitch || c->sub_h) return hop_set_err(c, HOP_ERR_ARG, "hop_decode_frame: a stacked context decodes no picture (one picture per context)");
-  if (c->shard_world > 1) return hop_set_err(c, HOP_ERR_ARG, "hop_decode_frame: a sharded context decodes no picture");
-  if (p->schedule != 0 && p->schedule != 1) return hop_set_err(c, HOP_ERR_ARG, "hop_decode_frame: schedule %d", p->schedule);
-  if (p->plain_intra != 0 && p->plain_intra != 1) return hop_set_err(c, HOP_ERR_ARG, "hop_decode_frame: plain_intra %d", p->plain_intra);
-  if (!p->plain_intra && (c->bd_y != 8 || c->bd_c != 8)) return hop_set_err(c, HOP_ERR_ARG, "hop_decode_frame: the HOP configuration is 8 bit, the context is %d bit", c->bd_y);
+static int dec_pictures(const hop_ctx* c, int* ph) {
+  *ph = c->sub_pitch ? c->sub_h : c->pic_h;
+  return c->sub_pitch ? (c->pic_h - c->sub_h) / c->sub_pitch + 1 : 1;
+}
+
+// internal: what hop_decode_frame, hop_decode_stack and hop_access_units_decode (csrc/k_stream.hip) share -- the checks, the plan of every picture of the context
+// (from the host parts; nothing is enqueued before it stands), the reset of the SS reference and one launch per level, picture k's CTUs at [k * n_ctu, (k + 1) * n_ctu).
+// d_parts == NULL: parts and `levels` (host) are uploaded into the scratch area.  Otherwise both are on the device already -- d_parts, d_levels, and d_order with room
+// for one int32 per CTU of the stack, in memory the caller keeps in place until this returns -- and `levels` is not read.  Synchronous.
+extern "C" __attribute__((visibility("hidden"))) int hop_dec_device(hop_ctx* c, const char* who, const char* noun, const hop_dec_params* p, const hop_cu_part* parts, const int32_t* levels,
+                                                                    const hop_cu_part* d_parts, const int32_t* d_levels, int32_t* d_order) {
+  if (c->shard_world > 1) return hop_set_err(c, HOP_ERR_ARG, "%s: a sharded context decodes no picture", who);
+  if (p->schedule != 0 && p->schedule != 1) return hop_set_err(c, HOP_ERR_ARG, "%s: schedule %d", who, p->schedule);
+  if (p->plain_intra != 0 && p->plain_intra != 1) return hop_set_err(c, HOP_ERR_ARG, "%s: plain_intra %d", who, p->plain_intra);
+  if (!p->plain_intra && (c->bd_y != 8 || c->bd_c != 8)) return hop_set_err(c, HOP_ERR_ARG, "%s: the HOP configuration is 8 bit, the context is %d bit", who, c->bd_y);
   const int off_y = 6 * (c->bd_y - 8), off_c = 6 * (c->bd_c - 8);
   if (p->qp < -off_y || p->qp > 51 || p->cb_qp_offset < -12 || p->cb_qp_offset > 12 || p->cr_qp_offset < -12 || p->cr_qp_offset > 12)
-    return hop_set_err(c, HOP_ERR_ARG, "hop_decode_frame: qp %d / offsets %d %d out of range", p->qp, p->cb_qp_offset, p->cr_qp_offset);
+    return hop_set_err(c, HOP_ERR_ARG, "%s: qp %d / offsets %d %d out of range", who, p->qp, p->cb_qp_offset, p->cr_qp_offset);
   c->levels_valid = false;                                              // the picture is no longer the one hop_encode_frame's resident levels belong to
-  const int wctu = (c->pic_w + 63) / 64, hctu = (c->pic_h + 63) / 64, n = wctu * hctu;
+  int ph; const int n_pic = dec_pictures(c, &ph);
+  const int wctu = (c->pic_w + 63) / 64, hctu = (ph + 63) / 64, n_ctu = wctu * hctu, n = n_ctu * n_pic;
   std::vector<int32_t> level(n);
   int32_t n_levels = 0;
   char err[256] = { 0 };
-  if (hop_dec_plan(c->pic_w, c->pic_h, !p->plain_intra, parts, p->schedule, level.data(), &n_levels, err, sizeof(err)) != HOP_OK)
+  if (hop_dec_plan_stack(c->pic_w, ph, n_pic, !p->plain_intra, parts, p->schedule, level.data(), &n_levels, noun, err, sizeof(err)) != HOP_OK)
     return hop_set_err(c, HOP_ERR_ARG, "%s", err);
-  // the CTUs level by level (counting sort; raster order inside a level)
+  // the CTUs of all pictures level by level (counting sort; inside a level picture after picture, raster order inside a picture)
   std::vector<int32_t> first(n_levels + 1, 0), order(n);
   for (int a = 0; a < n; a++) first[level[a] + 1]++;
   for (int l = 0; l < n_levels; l++) first[l + 1] += first[l];
@@ -246,28 +265,50 @@ extern "C" int hop_decode_frame(hop_ctx* c, const hop_dec_params* p, const hop_c
     const int q = std::min(57, std::max(-off_c, p->qp + o));
     A.qp_scaled[k] = q < 0 ? q + off_c : chroma_scale[q] + off_c;
   }
-  // parts, levels and the order uploaded once
-  const size_t b_parts = sizeof(hop_cu_part) * 256 * (size_t)n, b_levels = sizeof(int32_t) * 6144 * (size_t)n;
-  const size_t o_levels = (b_parts + 255) & ~(size_t)255, o_order = (o_levels + b_levels + 255) & ~(size_t)255, total = o_order + sizeof(int32_t) * (size_t)n;
-  void* buf; int r = hop_scratch(c, total, &buf); if (r) return r;
-  char* b = (char*)buf;
   hipError_t e = hipSetDevice(c->device);
-  if (e == hipSuccess) e = hipMemcpyAsync(b, parts, b_parts, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(b + o_levels, levels, b_levels, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(b + o_order, order.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream);
-  if (e != hipSuccess) return hop_set_err(c, HOP_ERR_DEVICE, "hop_decode_frame: upload: %s", hipGetErrorString(e));
-  if (!p->plain_intra) { r = hop_launch_ssref_reset(c); if (r) return r; }
-  A.parts = (const hop_cu_part*)b; A.levels = (const int32_t*)(b + o_levels);
+  if (!d_parts) {                                                       // parts and levels from the host: uploaded once, the order behind them
+    const size_t b_parts = sizeof(hop_cu_part) * 256 * (size_t)n, b_levels = sizeof(int32_t) * 6144 * (size_t)n;
+    const size_t o_levels = (b_parts + 255) & ~(size_t)255, o_order = (o_levels + b_levels + 255) & ~(size_t)255, total = o_order + sizeof(int32_t) * (size_t)n;
+    void* buf; const int r = hop_scratch(c, total, &buf); if (r) return r;
+    char* b = (char*)buf;
+    if (e == hipSuccess) e = hipMemcpyAsync(b, parts, b_parts, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(b + o_levels, levels, b_levels, hipMemcpyHostToDevice, c->stream);
+    d_parts = (const hop_cu_part*)b; d_levels = (const int32_t*)(b + o_levels); d_order = (int32_t*)(b + o_order);
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(d_order, order.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream);
+  if (e != hipSuccess) return hop_set_err(c, HOP_ERR_DEVICE, "%s: upload: %s", who, hipGetErrorString(e));
+  if (!p->plain_intra) { const int r = hop_launch_ssref_reset(c); if (r) return r; }
+  A.parts = d_parts; A.levels = d_levels;
   A.pic = hop_make_pics(c); A.pic.org_y = A.pic.org_cb = A.pic.org_cr = nullptr;      // (hop_ctx_set_row_limit is an encoder's: k_dec_ctu instantiates pred_inter_body<false>, which has no limited reads at all)
   A.pic_tu = A.pic; A.pic_tu.org_y = A.pic.pred_y; A.pic_tu.org_cb = A.pic.pred_cb; A.pic_tu.org_cr = A.pic.pred_cr;
   for (int k = 0; k < 3; k++) { A.rec[k] = c->rec[k]; A.ss00[k] = c->ss00[k]; }
   A.wctu = wctu; A.commit = !p->plain_intra;
+  A.n_ctu = n_ctu; A.sub_h = ph; A.sub_pitch = c->sub_pitch;
   for (int l = 0; l < n_levels; l++) {                                  // one launch per level, ordered by the stream alone
-    A.order = (const int32_t*)(b + o_order) + first[l];
-    hipLaunchKernelGGL(k_dec_ctu, dim3(first[l + 1] - first[l]), dim3(256), 0, c->stream, A);
+    A.order = d_order + first[l];
+    if (first[l + 1] > first[l]) hipLaunchKernelGGL(k_dec_ctu, dim3(first[l + 1] - first[l]), dim3(256), 0, c->stream, A);
   }
   e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) return hop_set_err(c, HOP_ERR_DEVICE, "hop_decode_frame: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return hop_set_err(c, HOP_ERR_DEVICE, "%s: %s", who, hipGetErrorString(e));
   return HOP_OK;
+}
+
+extern "C" int hop_decode_frame(hop_ctx* c, const hop_dec_params* p, const hop_cu_part* parts, const int32_t* levels) {
+  if (!c || !p || !parts || !levels) return hop_set_err(c, HOP_ERR_ARG, "hop_decode_frame: bad argument");
+  if (c->sub_pitch || c->sub_h) return hop_set_err(c, HOP_ERR_ARG, "hop_decode_frame: a stacked context decodes no picture (one picture per context)");
+  return hop_dec_device(c, "hop_decode_frame", "picture", p, parts, levels, nullptr, nullptr, nullptr);
+}
+
+extern "C" int hop_decode_stack(hop_ctx* c, const hop_dec_params* p, const hop_cu_part* parts, const int32_t* levels) {
+  if (!c || !p || !parts || !levels) return hop_set_err(c, HOP_ERR_ARG, "hop_decode_stack: bad argument");
+  return hop_dec_device(c, "hop_decode_stack", "picture", p, parts, levels, nullptr, nullptr, nullptr);
+}
+
+// host only; defined here, not in host/hop_decode.cpp, because the reason of a refusal goes where hop_last_error(NULL) reads it
+extern "C" int hop_decode_stack_schedule(int pic_w, int sub_h, int n_pictures, const hop_cu_part* parts, int schedule, int32_t* ctu_level, int32_t* n_levels) {
+  char err[256] = { 0 };
+  const int r = hop_dec_plan_stack(pic_w, sub_h, n_pictures, 1, parts, schedule, ctu_level, n_levels, "picture", err, sizeof(err));
+  if (r) hop_set_err(nullptr, r, "%s", err);
+  return r;
 }

@@ -28,6 +28,10 @@ int hop_parse_check(int pic_w, int pic_h, int bit_depth, int n_pic, const hop_sl
                     const hop_cu_part* parts, const hop_sao_param* sao, size_t* total, char* err, size_t errn);     // host/hop_parse.cpp
 __attribute__((visibility("hidden"))) int hop_parse_device(hop_ctx* c, const hop_slice_data_params* p, const uint8_t* data, const uint8_t* d_data, const uint32_t* substream_bytes,
                                                            int32_t n_substreams, hop_cu_part* parts, int32_t* levels, hop_sao_param* sao, size_t front);
+struct hop_parse_where { const hop_cu_part* d_parts; const int32_t* d_levels; size_t end; };   // where the parser left its outputs on the device; the end of its work area
+__attribute__((visibility("hidden"))) int hop_parse_device_at(hop_ctx* c, const char* who, const char* noun, const hop_slice_data_params* p, const uint8_t* data, const uint8_t* d_data,
+                                                              const unsigned long long* offsets, const uint32_t* substream_bytes, int32_t n_substreams, hop_cu_part* parts,
+                                                              int32_t* levels, hop_sao_param* sao, size_t front, hop_parse_where* where);
 }
 
 namespace {
@@ -103,10 +107,11 @@ static ParLayout par_layout(size_t front, int n_pic, int n, int hctu, int n_bloc
   return L;
 }
 
-// internal: an upper bound of what hop_parse_device adds to the scratch area behind `front` bytes of its caller's, for a context of one picture
+// internal: an upper bound of what hop_parse_device adds to the scratch area behind `front` bytes of its caller's, for the picture(s) of the context, n_substreams each
 extern "C" __attribute__((visibility("hidden"))) size_t hop_parse_work_bytes(const hop_ctx* c, size_t data_bytes, int n_substreams) {
-  const int wctu = (c->pic_w + 63) / 64, hctu = (c->pic_h + 63) / 64;
-  return par_layout(0, 1, wctu * hctu, hctu, n_substreams, true, true, data_bytes + 256).end + 256;
+  const int n_pic = c->sub_pitch ? (c->pic_h - c->sub_h) / c->sub_pitch + 1 : 1, ph = c->sub_pitch ? c->sub_h : c->pic_h;
+  const int wctu = (c->pic_w + 63) / 64, hctu = (ph + 63) / 64;
+  return par_layout(0, n_pic, wctu * hctu, hctu, n_pic * n_substreams, true, true, data_bytes + 256).end + 256;
 }
 
 extern "C" int hop_slice_data_parse(hop_ctx* c, const hop_slice_data_params* p, const uint8_t* data, const uint32_t* substream_bytes, int32_t n_substreams,
@@ -119,7 +124,17 @@ extern "C" int hop_slice_data_parse(hop_ctx* c, const hop_slice_data_params* p, 
 // the caller sized with hop_parse_work_bytes so that it does not move here): hop_access_unit_decode hands over what its compact kernel wrote
 extern "C" __attribute__((visibility("hidden"))) int hop_parse_device(hop_ctx* c, const hop_slice_data_params* p, const uint8_t* data, const uint8_t* d_data, const uint32_t* substream_bytes, int32_t n_substreams,
                                 hop_cu_part* parts, int32_t* levels, hop_sao_param* sao, size_t front) {
-  if (!c || !p || (!data && !d_data) || !substream_bytes || !parts) return hop_set_err(c, HOP_ERR_ARG, "hop_slice_data_parse: bad argument");
+  return hop_parse_device_at(c, "hop_slice_data_parse", "picture", p, data, d_data, nullptr, substream_bytes, n_substreams, parts, levels, sao, front, nullptr);
+}
+
+// internal: the same with the substreams wherever they lie -- offsets (host, may be NULL: back to back): where substream i starts, counted from d_data, all of it inside
+// the first `front` bytes of the scratch area -- and with the outputs left in the work area for the next kernels: `where` (may be NULL) says where.  With `where` the
+// levels are parsed into the work area also when `levels` is NULL: hop_access_units_decode (csrc/k_stream.hip) hands them to k_dec_ctu where they lie and downloads them
+// only for a caller who asks.  who / noun: how an error names the entry and a picture ("picture", "access unit").
+extern "C" __attribute__((visibility("hidden"))) int hop_parse_device_at(hop_ctx* c, const char* who, const char* noun, const hop_slice_data_params* p, const uint8_t* data, const uint8_t* d_data,
+                                const unsigned long long* offsets, const uint32_t* substream_bytes, int32_t n_substreams, hop_cu_part* parts, int32_t* levels, hop_sao_param* sao,
+                                size_t front, hop_parse_where* where) {
+  if (!c || !p || (!data && !d_data) || (offsets && !d_data) || !substream_bytes || !parts) return hop_set_err(c, HOP_ERR_ARG, "hop_slice_data_parse: bad argument");
   if (c->shard_world > 1) return hop_set_err(c, HOP_ERR_ARG, "hop_slice_data_parse: a sharded context parses no slice data");
   if (c->bd_y != c->bd_c) return hop_set_err(c, HOP_ERR_ARG, "hop_slice_data_parse: luma and chroma bit depths differ");
   const int n_pic = c->sub_pitch ? (c->pic_h - c->sub_h) / c->sub_pitch + 1 : 1, ph = c->sub_pitch ? c->sub_h : c->pic_h;
@@ -131,28 +146,35 @@ extern "C" __attribute__((visibility("hidden"))) int hop_parse_device(hop_ctx* c
   const int wctu = (c->pic_w + 63) / 64, hctu = (ph + 63) / 64, n = wctu * hctu;
   const int n_sub = n_substreams, n_blocks = n_pic * n_sub;
   std::vector<unsigned long long> offs((size_t)n_blocks);
-  { unsigned long long at = 0; for (int i = 0; i < n_blocks; i++) { offs[i] = at; at += substream_bytes[i]; } }
-  const size_t units = (size_t)n * n_pic * 256, parts_bytes = sizeof(hop_cu_part) * units, level_bytes = levels ? sizeof(int32_t) * 6144 * (size_t)n * n_pic : 0,
+  { unsigned long long at = 0; for (int i = 0; i < n_blocks; i++) { offs[i] = offsets ? offsets[i] : at; at += substream_bytes[i]; } }
+  const bool dev_levels = levels != nullptr || where != nullptr;
+  const size_t units = (size_t)n * n_pic * 256, parts_bytes = sizeof(hop_cu_part) * units, level_bytes = dev_levels ? sizeof(int32_t) * 6144 * (size_t)n * n_pic : 0,
                sao_bytes = sao ? sizeof(hop_sao_param) * 3 * (size_t)n * n_pic : 0;
-  const ParLayout L = par_layout(front, n_pic, n, hctu, n_blocks, levels != nullptr, sao != nullptr, d_data ? 0 : total + 256);
+  const ParLayout L = par_layout(front, n_pic, n, hctu, n_blocks, dev_levels, sao != nullptr, d_data ? 0 : total + 256);
   const size_t o_parts = L.o_parts, o_levels = L.o_levels, o_sao = L.o_sao, o_init = L.o_init, o_entry = L.o_entry, o_offs = L.o_offs, o_sizes = L.o_sizes, o_state = L.o_state,
                o_data = L.o_data;
   if (d_data && (!c->scratch || L.end > c->scratch_bytes)) return hop_set_err(c, HOP_ERR_STATE, "hop_slice_data_parse: the caller's scratch area of %zu bytes does not hold %zu", c->scratch_bytes, L.end);
   void* buf; r = hop_scratch(c, L.end, &buf); if (r) return r;
   char* b = (char*)buf;
+  if (offsets) {                                                           // every substream inside the caller's part of the scratch area
+    const size_t base = (size_t)((const char*)d_data - b);
+    for (int i = 0; i < n_blocks; i++)
+      if ((const char*)d_data < b || base + offs[i] + substream_bytes[i] > front) return hop_set_err(c, HOP_ERR_STATE, "%s: substream %d lies outside the caller's %zu bytes", who, i, front);
+  }
   HIPCHK(c, hipSetDevice(c->device));
   if (!d_data) HIPCHK(c, hipMemcpyAsync(b + o_data, data, total, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(b + o_init, init, EN_STATES, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(b + o_offs, offs.data(), sizeof(unsigned long long) * n_blocks, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(b + o_sizes, substream_bytes, sizeof(uint32_t) * n_blocks, hipMemcpyHostToDevice, c->stream));
-  if (levels) HIPCHK(c, hipMemsetAsync(b + o_levels, 0, level_bytes, c->stream));       // lane 0 stores the non-zero levels only
+  if (dev_levels) HIPCHK(c, hipMemsetAsync(b + o_levels, 0, level_bytes, c->stream));   // lane 0 stores the non-zero levels only
   if (sao) HIPCHK(c, hipMemsetAsync(b + o_sao, 0, sao_bytes, c->stream));
   HIPCHK(c, hipMemsetAsync(b + o_state, 0, sizeof(ParState) * n_blocks, c->stream));
   HIPCHK(c, hipMemsetAsync(b + o_entry, 0, (size_t)n_pic * hctu * EN_STATES, c->stream));
   ParArgs A;
   A.pic.e.pic_w = c->pic_w; A.pic.e.pic_h = ph; A.pic.e.wctu = wctu; A.pic.e.hctu = hctu;
   A.pic.e.i_slice = p->slice_type == 2; A.pic.e.sao_luma = p->sao_luma; A.pic.e.sao_chroma = p->sao_chroma; A.pic.e.sao_max_offset = (1 << (std::min(c->bd_y, 10) - 5)) - 1;
-  A.pic.parts = (hop_cu_part*)(b + o_parts); A.pic.levels = levels ? (int32_t*)(b + o_levels) : nullptr; A.pic.sao = sao ? (hop_sao_param*)(b + o_sao) : nullptr;
+  A.pic.parts = (hop_cu_part*)(b + o_parts); A.pic.levels = dev_levels ? (int32_t*)(b + o_levels) : nullptr; A.pic.sao = sao ? (hop_sao_param*)(b + o_sao) : nullptr;
+  if (where) { where->d_parts = A.pic.parts; where->d_levels = A.pic.levels; where->end = L.end; }
   A.pic.e.parts = A.pic.parts; A.pic.e.levels = A.pic.levels; A.pic.e.sao = A.pic.sao; A.pic.e.scans = c->rdoq_scans;
   A.pic.wpp = p->wpp; A.pic.sao_shift = c->bd_y - std::min(c->bd_y, 10); A.pic.mi_size = p->mi_size; A.pic.mi_merge = !p->plain_intra;
   A.n_pic = n_pic; A.n_sub = n_sub;
@@ -180,12 +202,12 @@ extern "C" __attribute__((visibility("hidden"))) int hop_parse_device(hop_ctx* c
   if (e == hipSuccess && levels) e = hipMemcpyAsync(levels, b + o_levels, level_bytes, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess && sao) e = hipMemcpyAsync(sao, b + o_sao, sao_bytes, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) return hop_set_err(c, HOP_ERR_DEVICE, "hop_slice_data_parse: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return hop_set_err(c, HOP_ERR_DEVICE, "%s: %s", who, hipGetErrorString(e));
   for (int i = 0; i < n_blocks; i++) {
     const uint32_t f = st[i].flags;
     if (!f) continue;
     const int first = p->wpp ? (i % n_sub) * wctu : 0;
-    return hop_set_err(c, HOP_ERR_ARG, "hop_slice_data_parse: substream %d of picture %d, CTU %d: %s (%u of %u bytes consumed)", i % n_sub, i / n_sub,
+    return hop_set_err(c, HOP_ERR_ARG, "%s: substream %d of %s %d, CTU %d: %s (%u of %u bytes consumed)", who, i % n_sub, noun, i / n_sub,
                        st[i].err_ctu < 0 ? first : st[i].err_ctu,
                        (f & PA_ERR_END) ? "the stream ran past the substream's end" : (f & PA_ERR_RANGE) ? "a value out of range" : "a terminating bin or the consumed length is wrong",
                        st[i].pos, substream_bytes[i]);

@@ -21,6 +21,7 @@
 // No kernel looks at another workgroup's progress.
 // The way back -- hop_rbsp_unescape, hop_access_unit_read, hop_access_unit_decode -- is further down: k_une_count / k_une_scan / k_une_compact remove emulation
 // prevention (the syntax is host/hop_stream_read.cpp), and the decode entry hands the compact kernel's output to the parser's kernels (csrc/k_parse.hip).
+// hop_access_units_decode, at the end, does it for the n pictures of a stacked context at once, the access units as the unescape grid's y dimension.
 #include <string.h>
 #include <algorithm>
 #include <vector>
@@ -39,6 +40,11 @@ void hop_strm_hash_plane(int method, int bit_depth, const int16_t* plane, int w,
 size_t hop_parse_work_bytes(const hop_ctx* c, size_t data_bytes, int n_substreams);                                                                         // k_parse.hip
 int hop_parse_device(hop_ctx* c, const hop_slice_data_params* p, const uint8_t* data, const uint8_t* d_data, const uint32_t* substream_bytes, int32_t n_substreams,
                      hop_cu_part* parts, int32_t* levels, hop_sao_param* sao, size_t front);
+struct hop_parse_where { const hop_cu_part* d_parts; const int32_t* d_levels; size_t end; };
+int hop_parse_device_at(hop_ctx* c, const char* who, const char* noun, const hop_slice_data_params* p, const uint8_t* data, const uint8_t* d_data, const unsigned long long* offsets,
+                        const uint32_t* substream_bytes, int32_t n_substreams, hop_cu_part* parts, int32_t* levels, hop_sao_param* sao, size_t front, hop_parse_where* where);
+int hop_dec_device(hop_ctx* c, const char* who, const char* noun, const hop_dec_params* p, const hop_cu_part* parts, const int32_t* levels, const hop_cu_part* d_parts, const int32_t* d_levels,
+                   int32_t* d_order);                                                                                                                         // k_decode.hip
 }
 #include "../host/hop_stream_read.h"
 
@@ -795,5 +801,151 @@ extern "C" int hop_access_unit_decode(hop_ctx* c, const uint8_t* au, size_t au_b
     for (int k = 0; k < 3; k++) hash_match[k] = !memcmp(got[k], a.digest[k], 16);
   }
   *info = a.info;
+  return HOP_OK;
+}
+
+// ---- n access units into the n pictures of a stacked context ----
+// One upload of the stream, one set of unescape launches with the access units as the grid's y dimension, one parse, one decode, one pass of each loop filter: what
+// hop_access_unit_decode does per picture, done once for the stack.  The scratch area is laid out after the host pass over every access unit's syntax, when all sizes are
+// known, and does not move afterwards: the stream and the unescape's records and outputs first (`front` bytes), the parser's work area behind them, then the decoder's
+// CTU order.  The parser reads each substream where the compact kernel left it (its device offset) and k_dec_ctu reads parts and levels where the parser left them.
+namespace {
+const char* strip_prefix(const char* s, const char* prefix) { const size_t n = strlen(prefix); return strncmp(s, prefix, n) ? s : s + n; }
+
+// the first field of the slice parameters in which b differs from a, or NULL
+const char* slice_params_differ(const hop_slice_data_params& a, const hop_slice_data_params& b, int* va, int* vb) {
+  const struct { const char* name; int32_t x, y; } f[7] = { { "qp", a.qp, b.qp }, { "slice_type", a.slice_type, b.slice_type }, { "wpp", a.wpp, b.wpp },
+    { "plain_intra", a.plain_intra, b.plain_intra }, { "sao_luma", a.sao_luma, b.sao_luma }, { "sao_chroma", a.sao_chroma, b.sao_chroma }, { "mi_size", a.mi_size, b.mi_size } };
+  for (int k = 0; k < 7; k++) if (f[k].x != f[k].y) { *va = f[k].x; *vb = f[k].y; return f[k].name; }
+  return nullptr;
+}
+}  // namespace
+
+extern "C" int hop_access_units_decode(hop_ctx* c, const uint8_t* stream, const size_t* au_bytes, int32_t n_au, const hop_stream_info* active, hop_stream_info* info,
+                                       int32_t (*hash_match)[3], hop_cu_part* parts, int32_t* levels, hop_sao_param* sao_coded) {
+  static const char who[] = "hop_access_units_decode";
+  if (!c || !stream || !au_bytes || n_au < 1 || !info || !hash_match) return hop_set_err(c, HOP_ERR_ARG, "%s: bad argument", who);
+  if (c->shard_world > 1) return hop_set_err(c, HOP_ERR_ARG, "%s: a sharded context reads no stream", who);
+  if (c->bd_y != c->bd_c) return hop_set_err(c, HOP_ERR_ARG, "%s: luma and chroma bit depths differ", who);
+  int ph; const int n_pic = pictures_of(c, &ph);
+  if (n_au != n_pic) return hop_set_err(c, HOP_ERR_ARG, "%s: %d access units, the context holds %d picture%s (a shorter tail of a sequence takes a context of its own)", who, n_au, n_pic, n_pic > 1 ? "s" : "");
+  const int wctu = (c->pic_w + 63) / 64, hctu = (ph + 63) / 64, n_ctu = wctu * hctu;
+  const size_t n = (size_t)n_ctu * n_pic;
+  // 1. the host pass over every access unit's syntax: access unit k against the nearest earlier one of this call that carried parameter sets, else against `active`
+  std::vector<hop_strm_au> a(n_au);
+  std::vector<size_t> au_at(n_au);
+  const int dims[3] = { c->pic_w, ph, c->bd_y };
+  char err[256];
+  size_t stream_bytes = 0, payload_total = 0;
+  {
+    const hop_stream_info* act = active;
+    for (int k = 0; k < n_au; k++) {
+      au_at[k] = stream_bytes;
+      const int r = hop_strm_read_syntax(stream + stream_bytes, au_bytes[k], act, dims, hctu, &a[k], err, sizeof(err));
+      if (r) return hop_set_err(c, r, "%s: access unit %d: %s", who, k, strip_prefix(err, "hop_access_unit_read: "));
+      int v0 = 0, vk = 0;
+      if (const char* field = slice_params_differ(a[0].info.params.slice, a[k].info.params.slice, &v0, &vk))
+        return hop_set_err(c, HOP_ERR_ARG, "%s: access unit %d: %s is %d, access unit 0 has %d (one parse serves all pictures of a stack)", who, k, field, vk, v0);
+      if (a[k].info.params.parameter_sets) act = &a[k].info;
+      if (stream_bytes + au_bytes[k] < stream_bytes) return hop_set_err(c, HOP_ERR_ARG, "%s: the access units' sizes overflow", who);
+      stream_bytes += au_bytes[k];
+      payload_total += a[k].nal_len - (size_t)a[k].info.header_bytes;
+    }
+  }
+  const hop_slice_data_params sl = a[0].info.params.slice;
+  const bool sao_on = sl.sao_luma || sl.sao_chroma;
+  const int n_sub = (int)a[0].seg.size(), n_seg = n_sub * n_au;       // (every access unit has the picture's CTU rows, or 1: the reader checked it)
+  for (int k = 1; k < n_au; k++) if ((int)a[k].seg.size() != n_sub) return hop_set_err(c, HOP_ERR_ARG, "%s: access unit %d: %zu substreams, access unit 0 has %d", who, k, a[k].seg.size(), n_sub);
+  // the scratch area, sized once
+  std::vector<size_t> o_out(n_au), chunk_at(n_au);
+  size_t end = 0, chunks_total = 0; uint32_t max_chunks = 0;
+  auto seg = [&](size_t bytes) { const size_t at = align256(end); end = at + bytes; return at; };
+  for (int k = 0; k < n_au; k++) { chunk_at[k] = chunks_total; const uint32_t nc = chunks_of(a[k].nal_len - (size_t)a[k].info.header_bytes); chunks_total += nc; max_chunks = std::max(max_chunks, nc); }
+  const size_t o_in = seg(stream_bytes + ESC_LANE + 3), o_ends = seg(sizeof(uint32_t) * n_seg), o_cnt = seg(sizeof(uint32_t) * n_seg), o_chunks = seg(sizeof(uint32_t) * chunks_total),
+               o_jobs = seg(sizeof(UneJob) * n_au), o_totals = seg(sizeof(unsigned long long) * n_au), o_viol = seg(sizeof(uint32_t) * n_au);
+  for (int k = 0; k < n_au; k++) o_out[k] = seg(a[k].nal_len - (size_t)a[k].info.header_bytes + ESC_LANE);
+  const size_t front = align256(end), o_order = align256(front + hop_parse_work_bytes(c, 0, n_sub)), total = o_order + sizeof(int32_t) * n;
+  void* buf; int r = hop_scratch(c, total, &buf); if (r) return r;
+  char* b = (char*)buf;
+  HIPCHK(c, hipSetDevice(c->device));
+  // 2. emulation prevention removed from every access unit's slice data; the RBSP stays on the device
+  std::vector<uint32_t> ends(n_seg);
+  std::vector<UneJob> J(n_au);
+  for (int k = 0; k < n_au; k++) {
+    const int back = std::min(2, (int)a[k].info.header_bytes);
+    const size_t payload = a[k].nal_len - (size_t)a[k].info.header_bytes;
+    size_t at = 0;
+    for (int i = 0; i < n_sub; i++) { at += a[k].seg[i]; ends[(size_t)k * n_sub + i] = (uint32_t)at; }
+    UneJob& j = J[k];
+    j.in = (const uint8_t*)(b + o_in) + au_at[k] + a[k].nal_at + a[k].info.header_bytes - back; j.lookback = (uint32_t)back; j.total = (uint32_t)payload;
+    j.seg_end = (const uint32_t*)(b + o_ends) + (size_t)k * n_sub; j.n_seg = (uint32_t)n_sub; j.seg_cnt = (uint32_t*)(b + o_cnt) + (size_t)k * n_sub;
+    j.chunk_cnt = (uint32_t*)(b + o_chunks) + chunk_at[k]; j.n_chunks = chunks_of(payload);
+    j.out = (uint8_t*)(b + o_out[k]); j.out_cap = payload; j.out_total = (unsigned long long*)(b + o_totals) + k; j.violations = (uint32_t*)(b + o_viol) + k;
+  }
+  HIPCHK(c, hipMemcpyAsync(b + o_in, stream, stream_bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(b + o_ends, ends.data(), sizeof(uint32_t) * n_seg, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(b + o_cnt, 0, sizeof(uint32_t) * n_seg, c->stream));
+  HIPCHK(c, hipMemsetAsync(b + o_viol, 0, sizeof(uint32_t) * n_au, c->stream));
+  HIPCHK(c, hipMemcpyAsync(b + o_jobs, J.data(), sizeof(UneJob) * n_au, hipMemcpyHostToDevice, c->stream));
+  {
+    const UneJob* dj = (const UneJob*)(b + o_jobs);
+    const int pr = hop_prof_begin(c, HOP_K_UNESCAPE, payload_total);
+    hipLaunchKernelGGL(k_une_count, dim3(max_chunks, n_au), dim3(ESC_THREADS), 0, c->stream, dj);
+    hipLaunchKernelGGL(k_une_scan, dim3(n_au), dim3(ESC_THREADS), 0, c->stream, dj);
+    hipLaunchKernelGGL(k_une_compact, dim3(max_chunks, n_au), dim3(ESC_THREADS), 0, c->stream, dj);
+    hop_prof_end(c, pr);
+    HIPCHK(c, hipGetLastError());
+  }
+  std::vector<unsigned long long> need(n_au);
+  std::vector<uint32_t> cnt(n_seg), viol(n_au), sizes(n_seg);
+  std::vector<unsigned long long> offs(n_seg);
+  HIPCHK(c, hipMemcpyAsync(need.data(), b + o_totals, sizeof(unsigned long long) * n_au, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(cnt.data(), b + o_cnt, sizeof(uint32_t) * n_seg, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(viol.data(), b + o_viol, sizeof(uint32_t) * n_au, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int k = 0; k < n_au; k++) {
+    unsigned long long dropped = 0, at = o_out[k];
+    for (int i = 0; i < n_sub; i++) {
+      const size_t s = (size_t)k * n_sub + i;
+      if (cnt[s] > a[k].seg[i]) return hop_set_err(c, HOP_ERR_DEVICE, "%s: access unit %d, substream %d: %u of %u bytes dropped", who, k, i, cnt[s], a[k].seg[i]);
+      dropped += cnt[s]; sizes[s] = a[k].seg[i] - cnt[s]; offs[s] = at; at += sizes[s];
+    }
+    if (need[k] + dropped != J[k].total) return hop_set_err(c, HOP_ERR_DEVICE, "%s: access unit %d: %llu bytes kept and %llu dropped of %u", who, k, need[k], dropped, J[k].total);
+    r = hop_strm_read_sizes(&sizes[(size_t)k * n_sub], n_sub, viol[k], err, sizeof(err));
+    if (r) return hop_set_err(c, r, "%s: access unit %d: %s", who, k, strip_prefix(err, "hop_access_unit_read: "));
+  }
+  // 3. one parse over the stack; 4. parts, SAO parameters and parser states to the host; 5. the levels only for a caller who asks
+  std::vector<hop_cu_part> own_parts; std::vector<hop_sao_param> own_sao;
+  if (!parts) { own_parts.resize(n * 256); parts = own_parts.data(); }
+  if (sao_on && !sao_coded) { own_sao.resize(n * 3); sao_coded = own_sao.data(); }
+  hop_parse_where where = { nullptr, nullptr, 0 };
+  r = hop_parse_device_at(c, who, "access unit", &sl, nullptr, (const uint8_t*)b, offs.data(), sizes.data(), n_sub, parts, levels, sao_on ? sao_coded : nullptr, front, &where);
+  if (r) return r;
+  if (where.end > o_order || (char*)c->scratch != b) return hop_set_err(c, HOP_ERR_STATE, "%s: the parser's work area ends at %zu, %zu were kept for it", who, where.end, o_order);
+  // 6. one decode over the parts and levels where the parser left them, one deblocking pass
+  hop_dec_params dp; dp.qp = sl.qp; dp.cb_qp_offset = 0; dp.cr_qp_offset = 0; dp.plain_intra = sl.plain_intra; dp.schedule = 0;
+  r = hop_dec_device(c, who, "access unit", &dp, parts, nullptr, where.d_parts, where.d_levels, (int32_t*)(b + o_order)); if (r) return r;
+  hop_deblock_params db; db.qp = sl.qp; db.beta_offset_div2 = 0; db.tc_offset_div2 = 0; db.cb_qp_offset = 0; db.cr_qp_offset = 0; db.disable = 0;
+  r = hop_deblock_frame(c, &db, parts); if (r) return r;
+  // 7. the SAO parameters resolved per picture (a merge never leaves its picture), one apply
+  if (sao_on) {
+    std::vector<hop_sao_param> recon(n * 3);
+    for (int k = 0; k < n_pic; k++)
+      if (hop_sao_reconstruct_params(n_ctu, wctu, c->bd_y, sao_coded + (size_t)k * n_ctu * 3, recon.data() + (size_t)k * n_ctu * 3))
+        return hop_set_err(c, HOP_ERR_ARG, "%s: access unit %d: the coded SAO parameters name a merge candidate that is not there", who, k);
+    r = hop_sao_apply(c, recon.data()); if (r) return r;
+  }
+  // 8. the hash of every picture, once per method the SEIs use, against each access unit's own
+  for (int k = 0; k < n_au; k++) hash_match[k][0] = hash_match[k][1] = hash_match[k][2] = -1;
+  for (int method = 1; method <= 3; method += 2) {
+    bool used = false;
+    for (int k = 0; k < n_au; k++) used = used || a[k].info.params.hash == method;
+    if (!used) continue;
+    std::vector<uint8_t> got((size_t)n_pic * 3 * 16);
+    r = hop_picture_hash(c, method, (uint8_t (*)[16])got.data()); if (r) return r;
+    for (int k = 0; k < n_au; k++)
+      if (a[k].info.params.hash == method) for (int comp = 0; comp < 3; comp++) hash_match[k][comp] = !memcmp(&got[((size_t)k * 3 + comp) * 16], a[k].digest[comp], 16);
+  }
+  for (int k = 0; k < n_au; k++) info[k] = a[k].info;
   return HOP_OK;
 }

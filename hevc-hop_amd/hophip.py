@@ -470,6 +470,47 @@ class Context:
         self.L.hop_decode_frame.argtypes = [ctypes.c_void_p] * 4
         self._chk(self.L.hop_decode_frame(self.h, ctypes.byref(p), parts.ctypes.data, levels.ctypes.data), "hop_decode_frame")
 
+    def decode_stack(self, parts, levels, qp=32, cb_qp_offset=0, cr_qp_offset=0, plain_intra=0, schedule=0):
+        """hop_decode_stack: decode_frame for every picture of a stacked context side by side -- parts and levels picture after picture, as encode_frame /
+        levels_download / slice_data_parse give them for a stack.  On an unstacked context it is decode_frame."""
+        parts = np.ascontiguousarray(parts, CU_PART_DTYPE); levels = np.ascontiguousarray(levels, np.int32)
+        n = self._n_ctu()
+        if parts.size != n * 256 or levels.size != n * 6144:
+            raise HopError("decode_stack: %d CTUs need (%d, 256) parts and (%d, 6144) levels" % (n, n, n))
+        p = DecParams(qp, cb_qp_offset, cr_qp_offset, plain_intra, schedule)
+        self.L.hop_decode_stack.argtypes = [ctypes.c_void_p] * 4
+        self._chk(self.L.hop_decode_stack(self.h, ctypes.byref(p), parts.ctypes.data, levels.ctypes.data), "hop_decode_stack")
+
+    def access_units_decode(self, aus, active=None, want_outputs=True, want_levels=True):
+        """hop_access_units_decode: a list of access units' bytes, one per picture of the context, to the pictures resident in it (recon_download, unstack).  Returns
+        (StreamInfo per picture, hash_match per picture [3]: 1 equal, 0 different, -1 not checked, parts, levels, coded SAO parameters or None -- the stack's, picture after
+        picture); want_outputs False: the three are not asked for (None); want_levels False: the levels alone are not (they then never leave the device)."""
+        aus = [bytes(a) for a in aus]
+        stream = np.frombuffer(b"".join(aus) or b"\0", np.uint8).copy()
+        sizes = (ctypes.c_size_t * max(1, len(aus)))(*[len(a) for a in aus])
+        n = self._n_ctu()
+        infos = (StreamInfo * max(1, len(aus)))()
+        match = np.full((max(1, len(aus)), 3), -2, np.int32)
+        out = [np.full(nb + PARSE_GUARD, 0xA5, np.uint8) if want_outputs and on else None
+               for nb, on in ((n * 256 * CU_PART_DTYPE.itemsize, True), (n * 6144 * 4, want_levels), (n * 3 * SAO_PARAM_DTYPE.itemsize, True))]
+        self.L.hop_access_units_decode.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32] + [ctypes.c_void_p] * 6
+        r = self.L.hop_access_units_decode(self.h, stream.ctypes.data, sizes, len(aus), None if active is None else ctypes.byref(active), infos, match.ctypes.data,
+                                           *[None if b is None else b.ctypes.data for b in out])
+        for b in out:
+            assert b is None or np.all(b[-PARSE_GUARD:] == 0xA5), "hop_access_units_decode stored past an output"
+        if r != 0:
+            e = HopError("hop_access_units_decode: %d %s" % (r, self.L.hop_last_error(self.h).decode()))
+            e.code = r
+            raise e
+        infos = [StreamInfo.from_buffer_copy(bytes(i)) for i in infos][:len(aus)]
+        if not want_outputs:
+            return infos, match.tolist(), None, None, None
+        parts = out[0][:-PARSE_GUARD].view(CU_PART_DTYPE).reshape(n, 256)
+        levels = None if out[1] is None else out[1][:-PARSE_GUARD].view(np.int32).reshape(n, 6144)
+        sl = infos[0].params.slice
+        sao = out[2][:-PARSE_GUARD].view(SAO_PARAM_DTYPE).reshape(n, 3) if (sl.sao_luma or sl.sao_chroma) else None
+        return infos, match.tolist(), parts, levels, sao
+
     def slice_data_write(self, parts, levels=None, sao_coded=None, qp=32, slice_type=3, wpp=0, plain_intra=0, sao_luma=None, sao_chroma=None, mi_size=16, capacity=None, guard=0):
         """hop_slice_data_write: the slice data of the context's picture(s) -- parts as encode_frame returned them, levels (n_ctu, 6144) int32 or None = the levels resident
         after encode_frame, sao_coded (n_ctu, 3) as sao_frame returned them or None (no SAO syntax; the flags default to whether it is given).  Returns (the substreams back to
@@ -834,6 +875,22 @@ def decode_schedule(W, H, parts, schedule=0, lib=None):
     r = L.hop_decode_schedule(W, H, parts.ctypes.data, schedule, lv.ctypes.data, ctypes.byref(nl))
     if r != 0:
         raise HopError("hop_decode_schedule: %d" % r)
+    return lv, int(nl.value)
+
+
+def decode_stack_schedule(W, sub_h, pictures, parts, schedule=0, lib=None):
+    """hop_decode_stack_schedule: (level of every CTU (pictures, n_ctu) int32, number of levels) -- the launches hop_decode_stack makes for a stack of `pictures`
+    pictures of W x sub_h; HopError, naming the picture, for refused parts"""
+    L = lib or load()
+    parts = np.ascontiguousarray(parts, CU_PART_DTYPE)
+    n = ((W + 63) // 64) * ((sub_h + 63) // 64)
+    if pictures < 1 or parts.size != pictures * n * 256:
+        raise HopError("decode_stack_schedule: %d pictures of %d CTUs need (%d, 256) parts" % (pictures, n, pictures * n))
+    lv = np.zeros((pictures, n), np.int32); nl = ctypes.c_int32(0)
+    L.hop_decode_stack_schedule.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    r = L.hop_decode_stack_schedule(W, sub_h, pictures, parts.ctypes.data, schedule, lv.ctypes.data, ctypes.byref(nl))
+    if r != 0:
+        raise HopError("hop_decode_stack_schedule: %d %s" % (r, L.hop_last_error(None).decode()))
     return lv, int(nl.value)
 
 

@@ -1,4 +1,5 @@
-// hop_decode.cpp -- host side of hop_decode_frame: the checks of the partition data and the schedule of the picture's CTUs (plain C++, no device code).
+// hop_decode.cpp -- host side of hop_decode_frame and hop_decode_stack: the checks of the partition data and the schedule of the picture's CTUs, and the merge of the
+// pictures' schedules for a stack (plain C++, no device code).
 //
 // The reference decoder reconstructs CTUs in raster order and the CUs of a CTU in z-order, and commits every CU to the SS reference as soon as it is decoded
 // (TDecCu::xDecompressCU -> xFindSSRef2Copy, TLibDecoder/TDecCu.cpp:383-476).  Samples of CUs not yet decoded read as the sentinel -1, and predictions do read them.
@@ -259,6 +260,33 @@ __attribute__((visibility("hidden"))) int hop_dec_plan(int pic_w, int pic_h, int
     top = std::max(top, lv);
   }
   *n_levels = top + 1;
+  return HOP_OK;
+}
+
+// internal: hop_dec_plan for the n_pic pictures of a stack (hop_decode_stack, csrc/k_decode.hip).  Every picture is planned alone, in its own coordinates; the plans
+// are merged by level, so launch l holds the level-l CTUs of all pictures and *n_levels is the maximum over the pictures, not the sum (raster: CTU a of every picture in
+// launch a).  parts and ctu_level: picture k's CTUs at [k * n_ctu, (k + 1) * n_ctu).  A refusal names the picture when there is more than one, by
+// `noun` ("picture"; "access unit" for hop_access_units_decode).
+__attribute__((visibility("hidden"))) int hop_dec_plan_stack(int pic_w, int sub_h, int n_pic, int allow_inter, const hop_cu_part* parts, int schedule, int32_t* ctu_level,
+                                                               int32_t* n_levels, const char* noun, char* err, size_t errn) {
+  if (n_pic < 1 || !parts || !ctu_level || !n_levels) {
+    if (err && errn) snprintf(err, errn, "hop_decode: bad argument");
+    return HOP_ERR_ARG;
+  }
+  const size_t n = (size_t)((pic_w + CTU - 1) / CTU) * ((sub_h + CTU - 1) / CTU);
+  int32_t top = 0;
+  for (int k = 0; k < n_pic; k++) {
+    char one[200] = { 0 };
+    int32_t nl = 0;
+    const int r = hop_dec_plan(pic_w, sub_h, allow_inter, parts + (size_t)k * n * 256, schedule, ctu_level + (size_t)k * n, &nl, one, sizeof(one));
+    if (r) {
+      const char* what = strncmp(one, "hop_decode: ", 12) ? one : one + 12;
+      if (err && errn) { if (n_pic > 1) snprintf(err, errn, "hop_decode: %s %d: %s", noun ? noun : "picture", k, what); else snprintf(err, errn, "%s", one); }
+      return r;
+    }
+    top = std::max(top, nl);
+  }
+  *n_levels = top;
   return HOP_OK;
 }
 

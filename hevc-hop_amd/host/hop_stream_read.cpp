@@ -254,8 +254,11 @@ HIDDEN int hop_strm_read_syntax(const uint8_t* au, size_t n, const hop_stream_in
   if (active) {
     const hop_slice_data_params& a = active->params.slice;
     const int a_sao = a.sao_luma || a.sao_chroma;
-    if (n_sets && (s.pic_w != active->pic_w || s.pic_h != active->pic_h || s.bit_depth != active->bit_depth || s.holo != !a.plain_intra || s.mi != a.mi_size || s.wpp != a.wpp ||
-                   s.sao != a_sao)) { e.say("the parameter sets contradict `active`"); return HOP_ERR_ARG; }
+    if (n_sets) {
+      const struct { const char* name; int got, want; } f[7] = { { "pic_w", s.pic_w, active->pic_w }, { "pic_h", s.pic_h, active->pic_h }, { "bit_depth", s.bit_depth, active->bit_depth },
+        { "plain_intra", !s.holo, a.plain_intra != 0 }, { "mi_size", s.mi, a.mi_size }, { "wpp", s.wpp, a.wpp }, { "the SAO flag", s.sao, a_sao } };
+      for (int k = 0; k < 7; k++) if (f[k].got != f[k].want) { e.say("the parameter sets contradict `active`: %s %d, `active` has %d", f[k].name, f[k].got, f[k].want); return HOP_ERR_ARG; }
+    }
     if (!n_sets) { s.pic_w = active->pic_w; s.pic_h = active->pic_h; s.bit_depth = active->bit_depth; s.holo = !a.plain_intra; s.mi = a.mi_size; s.wpp = a.wpp; s.sao = a_sao; }
   } else if (!n_sets) { e.say("the access unit carries no parameter sets and `active` is NULL"); return HOP_ERR_ARG; }
   if (s.pic_w <= 0 || s.pic_h <= 0 || (s.pic_w & 7) || (s.pic_h & 7) || s.pic_w > 65528 || s.pic_h > 65528 || (s.bit_depth != 8 && s.bit_depth != 10) || (s.holo != 0 && s.holo != 1) ||

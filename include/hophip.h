@@ -782,6 +782,19 @@ int hop_decode_frame(hop_ctx* ctx, const hop_dec_params* params, const hop_cu_pa
  * levels respect, for every CTU, its left, above-left, above and above-right neighbours and, for every SS / GT PU, the CTUs its prediction reads: a raster-earlier one
  * in a lower level, a raster-later one in a higher level. */
 int hop_decode_schedule(int pic_w, int pic_h, const hop_cu_part* parts, int schedule, int32_t* ctu_level, int32_t* n_levels);
+/* replaces: the same members as hop_decode_frame -- TDecCu::decompressCtu / xDecompressCU (TLibDecoder/TDecCu.cpp:383-476) with xReconIntraQT, xReconInter and
+ * xFindSSRef2Copy -- run by the reference once per view (TAppDecTop::decode, one decoder instance per stream), here for all pictures of a stacked context
+ * (hop_ctx_set_stack) side by side.  Semantics are hop_decode_frame's, applied to every picture: parts 256 and levels 6144 per CTU, picture k's CTUs at
+ * [k * n_ctu, (k + 1) * n_ctu) -- the layout hop_encode_frame, hop_levels_download and hop_slice_data_parse produce for a stack.  Every picture is planned alone, in its
+ * own coordinates, and the plans are merged: launch l holds the level-l CTUs of all pictures, so the number of launches is the maximum over the pictures, not the sum
+ * (schedule 1: CTU a of every picture in launch a).  A CTU addresses the planes by the rows of the stack; intra availability, the vector clip and the margins its commit
+ * extends are those of its own picture, so every picture comes out exactly as from hop_decode_frame on a context of its own.  On an unstacked context it behaves as
+ * hop_decode_frame.  Refused before anything is enqueued: a sharded context; malformed partition data in any picture, hop_last_error naming the picture. */
+int hop_decode_stack(hop_ctx* ctx, const hop_dec_params* params, const hop_cu_part* parts, const int32_t* levels);
+/* host only: hop_decode_schedule for a stack of n_pictures pictures of pic_w x sub_h -- the checks and the launches of hop_decode_stack.  ctu_level: one per CTU, picture
+ * after picture; picture k's levels are what hop_decode_schedule gives that picture alone; *n_levels: the maximum over the pictures.  A refusal returns HOP_ERR_ARG and
+ * leaves its reason, with the picture, where hop_last_error(NULL) reads it. */
+int hop_decode_stack_schedule(int pic_w, int sub_h, int n_pictures, const hop_cu_part* parts, int schedule, int32_t* ctu_level, int32_t* n_levels);
 /* host only: the CTUs (raster addresses, ascending) whose samples -- margin samples counted with the border sample they replicate -- the predictor of one PU
  * (hop_pred_inter) reads, luma and chroma; returns their number (only the first max_ctus are written), HOP_ERR_ARG for a footprint outside the padded plane. */
 int hop_decode_footprint(int pic_w, int pic_h, const hop_pred_job* pu, int32_t* ctus, int max_ctus);
@@ -992,6 +1005,22 @@ int hop_annexb_access_unit(const uint8_t* stream, size_t bytes, size_t* au_bytes
  * a parse error (HOP_ERR_ARG naming substream and CTU) leaves the context usable. */
 int hop_access_unit_decode(hop_ctx* ctx, const uint8_t* au, size_t au_bytes, const hop_stream_info* active, hop_stream_info* info, int32_t hash_match[3],
                            hop_cu_part* parts, int32_t* levels, hop_sao_param* sao_coded);
+/* replaces: TDecTop::decode with executeLoopFilters and the hash check of TAppDecTop (calcAndPrintHashStatus), as hop_access_unit_decode -- which the reference runs once
+ * per access unit and once per view's stream -- for n_au access units at once: access unit k becomes picture k of a stacked context (hop_ctx_set_stack; n_au must be the
+ * context's picture count, 1 on an unstacked one).  stream: the access units back to back, au_bytes[k] each.  They may be n pictures of one all-intra sequence (only the
+ * first carries parameter sets) or n independent streams of one geometry and configuration.  Access unit k is read against the info of the nearest earlier access unit of
+ * this call that carried parameter sets, or against `active` when there is none.  One parse serves all pictures: every access unit's params.slice must equal the first
+ * one's in every field (HOP_ERR_ARG naming the access unit and the field); poc, parameter_sets, hash and nal_type may differ.
+ * In order: the host pass over every access unit's syntax, after which the scratch area is sized once; one upload of the stream and one set of unescape launches, the
+ * access units side by side; one parse over the stack, every substream read where the unescape left it; parts, SAO parameters and parser states to the host (the plan
+ * and the deblocking's checks need the parts); the levels stay where the parser wrote them for k_dec_ctu and are downloaded only when levels != NULL; one
+ * hop_decode_stack body over device pointers; one hop_deblock_frame; hop_sao_reconstruct_params per picture and one hop_sao_apply; hop_picture_hash once per method the
+ * SEIs use, compared per picture with that access unit's SEI.
+ * info: n_au; hash_match[k][plane]: 1 equal, 0 different, -1 not checked (no SEI, or CRC); parts, levels, sao_coded: the stack's layout, each may be NULL.  Refusals as
+ * hop_access_unit_decode's (a sharded context; not a stacked one), each naming the access unit; a parse error names access unit, substream and CTU and leaves the context
+ * usable. */
+int hop_access_units_decode(hop_ctx* ctx, const uint8_t* stream, const size_t* au_bytes, int32_t n_au, const hop_stream_info* active, hop_stream_info* info /* n_au */,
+                            int32_t (*hash_match)[3] /* n_au */, hop_cu_part* parts, int32_t* levels, hop_sao_param* sao_coded /* each may be NULL */);
 
 /* ---- profiling (bench.py roofline): HIP events around every kernel launch on the context stream ---- */
 #define HOP_K_SS_SEARCH 0
