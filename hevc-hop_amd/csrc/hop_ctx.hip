@@ -53,10 +53,15 @@ static int walk_reserve(hop_ctx* c, size_t bytes) { return hop_reserve(c, &c->wa
 // The context's own stream -- the spine's short requests: predictions, searches, block copies -- runs at the highest priority, the views' streams (the candidate
 // evaluations, hundreds of long workgroups in flight) at the lowest: without it a 10 us prediction kernel waits for a free compute unit behind them (measured on the
 // 7728-wide picture: 0.15 ms -> 0.03 ms per prediction request, 27 -> 35 CTU/s).  HOP_STREAM_PRIO=0 turns it off.
-static hipError_t create_lanes(hop_ctx* c, unsigned stream_flags, bool highest_priority) {
+static hipError_t create_stream(hipStream_t* out, unsigned stream_flags, bool highest_priority) {
   int prio_lo = 0, prio_hi = 0; (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
   const char* f = getenv("HOP_STREAM_PRIO");
-  hipError_t e = (f && f[0] == '0') ? hipStreamCreateWithFlags(&c->stream, stream_flags) : hipStreamCreateWithPriority(&c->stream, stream_flags, highest_priority ? prio_hi : prio_lo);
+  return (f && f[0] == '0') ? hipStreamCreateWithFlags(out, stream_flags) : hipStreamCreateWithPriority(out, stream_flags, highest_priority ? prio_hi : prio_lo);
+}
+// (borrowed: the context's own stream is that one, hop_ctx_create_view_on)
+static hipError_t create_lanes(hop_ctx* c, unsigned stream_flags, bool highest_priority, hipStream_t borrowed = nullptr) {
+  hipError_t e = hipSuccess;
+  if (borrowed) { c->stream = borrowed; c->borrowed_stream = true; } else e = create_stream(&c->stream, stream_flags, highest_priority);
   for (int k = 0; k < HOP_MAX_LANES - 1 && e == hipSuccess; k++) {
     e = hipStreamCreateWithFlags(&c->xlane[k].stream, stream_flags);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_join[k], hipEventDisableTiming);
@@ -204,6 +209,30 @@ static bool intra_neighbours_ok(const hop_ctx* c, const hop_intra_job& j, int sh
   return true;
 }
 
+// The internal forms of hop_ctx_create_view (hop_dev.h): a view on a borrowed stream, the stream such views borrow, and moving a view to another one.
+int hop_view_stream_create(hop_ctx* parent, hipStream_t* out) {
+  if (!parent || !out) return hop_set_err(parent, HOP_ERR_ARG, "hop_view_stream_create: bad argument");
+  HIPCHK(parent, hipSetDevice(parent->device));
+  HIPCHK(parent, create_stream(out, hipStreamNonBlocking, false));
+  return HOP_OK;
+}
+void hop_view_set_stream(hop_ctx* view, hipStream_t borrowed) { if (view && view->borrowed_stream && borrowed) view->stream = borrowed; }
+int hop_ctx_create_view_on(hop_ctx* parent, hipStream_t borrowed, hop_ctx** out) {
+  if (!parent || !out) return hop_set_err(parent, HOP_ERR_ARG, "hop_ctx_create_view_on: bad argument");       // (a view of a view is one more view of the same pictures)
+  *out = nullptr;
+  hop_ctx* c = (hop_ctx*)calloc(1, sizeof(hop_ctx));
+  c->pic_w = parent->pic_w; c->pic_h = parent->pic_h; c->bd_y = parent->bd_y; c->bd_c = parent->bd_c; c->device = parent->device;
+  c->stride_y = parent->stride_y; c->stride_c = parent->stride_c; c->sub_h = parent->sub_h; c->sub_pitch = parent->sub_pitch; c->slots = parent->slots; c->fused_leaf_max = parent->fused_leaf_max; c->walk_max = parent->walk_max; c->ss_families = parent->ss_families; c->row_limit = parent->row_limit; c->lanes = 1; c->is_view = true;
+  c->org_y = parent->org_y; c->org_cb = parent->org_cb; c->org_cr = parent->org_cr;
+  for (int k = 0; k < 3; k++) { c->ss_alloc[k] = parent->ss_alloc[k]; c->ss_buf[k] = parent->ss_buf[k]; c->ss00[k] = parent->ss00[k]; c->pred[k] = parent->pred[k]; c->rec[k] = parent->rec[k]; }
+  c->entropy_bits = parent->entropy_bits; c->rdoq_scans = parent->rdoq_scans; c->have_orig = parent->have_orig; c->stash = parent->stash; c->stash_slots = parent->stash_slots; c->coefpic = parent->coefpic; c->coef_stash = parent->coef_stash;
+  hipError_t e = hipSetDevice(c->device);
+  if (e == hipSuccess) e = create_lanes(c, hipStreamNonBlocking, false, borrowed);
+  if (e != hipSuccess) { hop_set_err(parent, HOP_ERR_DEVICE, "hop_ctx_create_view_on: %s", hipGetErrorString(e)); hop_ctx_destroy(c); return HOP_ERR_DEVICE; }
+  *out = c;
+  return HOP_OK;
+}
+
 extern "C" {
 
 const char* hop_version(void) { return "hophip 0.1 gfx950"; }
@@ -269,21 +298,7 @@ int hop_ctx_create(hop_ctx** out, int pic_w, int pic_h, int bit_depth_y, int bit
 
 // A second handle on the same pictures with its own stream and work areas: requests issued through different views run concurrently on the device.  The caller keeps
 // their rectangles apart (the RD spine's CTU rows are a wavefront lag apart) and destroys the views before the parent.
-int hop_ctx_create_view(hop_ctx* parent, hop_ctx** out) {
-  if (!parent || !out) return hop_set_err(parent, HOP_ERR_ARG, "hop_ctx_create_view: bad argument");          // (a view of a view is one more view of the same pictures)
-  *out = nullptr;
-  hop_ctx* c = (hop_ctx*)calloc(1, sizeof(hop_ctx));
-  c->pic_w = parent->pic_w; c->pic_h = parent->pic_h; c->bd_y = parent->bd_y; c->bd_c = parent->bd_c; c->device = parent->device;
-  c->stride_y = parent->stride_y; c->stride_c = parent->stride_c; c->sub_h = parent->sub_h; c->sub_pitch = parent->sub_pitch; c->slots = parent->slots; c->fused_leaf_max = parent->fused_leaf_max; c->walk_max = parent->walk_max; c->ss_families = parent->ss_families; c->row_limit = parent->row_limit; c->lanes = 1; c->is_view = true;
-  c->org_y = parent->org_y; c->org_cb = parent->org_cb; c->org_cr = parent->org_cr;
-  for (int k = 0; k < 3; k++) { c->ss_alloc[k] = parent->ss_alloc[k]; c->ss_buf[k] = parent->ss_buf[k]; c->ss00[k] = parent->ss00[k]; c->pred[k] = parent->pred[k]; c->rec[k] = parent->rec[k]; }
-  c->entropy_bits = parent->entropy_bits; c->rdoq_scans = parent->rdoq_scans; c->have_orig = parent->have_orig; c->stash = parent->stash; c->stash_slots = parent->stash_slots; c->coefpic = parent->coefpic; c->coef_stash = parent->coef_stash;
-  hipError_t e = hipSetDevice(c->device);
-  if (e == hipSuccess) e = create_lanes(c, hipStreamNonBlocking, false);
-  if (e != hipSuccess) { hop_set_err(parent, HOP_ERR_DEVICE, "hop_ctx_create_view: %s", hipGetErrorString(e)); hop_ctx_destroy(c); return HOP_ERR_DEVICE; }
-  *out = c;
-  return HOP_OK;
-}
+int hop_ctx_create_view(hop_ctx* parent, hop_ctx** out) { return hop_ctx_create_view_on(parent, nullptr, out); }
 
 // Several independent pictures of equal size in one context, so that one batch of requests serves CTUs of all of them (hop_encode_frame codes them side by side): the
 // context's picture is their stack, picture k at rows k * sub_pitch .. k * sub_pitch + sub_h - 1, the rows between them unused.  The gap keeps every sample a picture's
@@ -341,7 +356,7 @@ void hop_ctx_destroy(hop_ctx* c) {
   void* ptrs[] = { c->org_y, c->org_cb, c->org_cr, c->ss_alloc[0], c->ss_alloc[1], c->ss_alloc[2], c->pred[0], c->pred[1], c->pred[2],
                    c->rec[0], c->rec[1], c->rec[2], c->scratch, c->stage, c->rqt_buf, c->walk_buf, c->rdoq_scans, c->entropy_bits, c->stash, c->coefpic, c->coef_stash };
   for (void* p : ptrs) if (p) (void)hipFree(p);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
+  if (c->stream && !c->borrowed_stream) (void)hipStreamDestroy(c->stream);
   for (int k = 0; k < HOP_MAX_LANES - 1; k++) {
     const hop_lane& x = c->xlane[k];
     if (x.stream) (void)hipStreamDestroy(x.stream);

@@ -57,6 +57,7 @@ struct hop_ctx : hop_lane {
   std::atomic<long> enc_progress; std::atomic<int> enc_cancel;   // hop_encode_progress / hop_encode_cancel: CTUs the running hop_encode_frame has retired; a request to stop it
   uint16_t* rd_fraction; int rd_fraction_n;   // host: hop_encode_frame's per-CTU carried fraction of the RD coder (hop_rd_fraction_download)
   bool   is_view;                    // hop_ctx_create_view: pictures, tables and stash belong to the parent; stream, scratch areas and profiling are its own
+  bool   borrowed_stream;            // hop_ctx_create_view_on: the view's stream is somebody else's too (work areas and profiling are still its own)
   char   err[512];
   // profiling (hop_profile_*): event pairs recorded around kernel launches, folded into the sums on read
   bool   prof_on;
@@ -249,3 +250,9 @@ int hop_launch_ssref_reset(hop_ctx* c);
 int hop_launch_ssref_commit(hop_ctx* c, int n, const int32_t* d_rect4, const int16_t* d_y, const int16_t* d_cb, const int16_t* d_cr, int packed);
 int hop_set_err(hop_ctx* c, int code, const char* fmt, ...);
 int hop_scratch(hop_ctx* c, size_t bytes, void** out);
+// hop_ctx_create_view's internal form (k_spine.hip: the buffer sets of the candidate evaluations): the view works on `borrowed`, a stream made by hop_view_stream_create
+// that it does not destroy, and hop_view_set_stream moves it -- a view with nothing queued -- to another such stream.  hop_view_stream_create makes the stream a view of
+// its own would get (non-blocking, lowest priority); the caller destroys it after the views that borrow it.
+int hop_ctx_create_view_on(hop_ctx* parent, hipStream_t borrowed, hop_ctx** out);
+int hop_view_stream_create(hop_ctx* parent, hipStream_t* out);
+void hop_view_set_stream(hop_ctx* view, hipStream_t borrowed);

@@ -204,19 +204,25 @@ using namespace hopspine;
 
 struct Bail { int code; };
 // wall time and calls per kind of request of the last hop_encode_frame (hop_encode_stats): 0 me_search, 1 pred_inter, 2 distortion, 3 valid_pattern, 4 inter_cu with
-// residual, 5 inter_cu without, 6 intra_cu, 7 recon stash, 8 commit, 9 the wait for the evaluation chains issued on streams of their own (then 4 - 6 hold the issue time only)
+// residual, 5 inter_cu without, 6 intra_cu, 7 recon stash, 8 commit, 9 the wait for the evaluation chains issued on streams of their own (then 4 - 6 hold the issue time only);
+// ms 15 / calls 13: the hand-over wait -- an evaluation group that found no free place waited for an earlier chain's end before it could be issued
 double g_stat_ms[16]; double g_stat_calls[16];
 std::mutex g_stat_lock;
 struct Tick { int k; std::chrono::steady_clock::time_point t0; explicit Tick(int k) : k(k), t0(std::chrono::steady_clock::now()) {}
               ~Tick() { const double d = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
                         std::lock_guard<std::mutex> g(g_stat_lock); g_stat_ms[k] += d; g_stat_calls[k] += 1; } };
+enum { STAT_HANDOVER_MS = 15, STAT_HANDOVER_CALLS = 13 };
 #define BK(call) do { int r_ = (call); if (r_ != HOP_OK) throw Bail{ r_ }; } while (0)
 #define BH(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { hop_set_err(c, HOP_ERR_DEVICE, "%s: %s", #call, hipGetErrorString(e_)); throw Bail{ HOP_ERR_DEVICE }; } } while (0)
 
 class HipBackend : public BatchInner {
  public:
   enum { MAXN = 2048, MAXP = 32768 };   // candidates of one class / predictor jobs in one batch (one per CTU row in flight, all pictures together)
-  explicit HipBackend(hop_ctx* ctx, bool sub = false) : c(ctx), arena(nullptr), is_sub_(sub), rr_(0) {
+  enum { MAX_STREAMS = 8, MAX_SETS = 16, DEFAULT_STREAMS = 4, DEFAULT_SETS = 8 };   // evaluation streams (HOP_SPINE_STREAMS) and buffer sets (HOP_SPINE_SETS)
+  // HOP_SPINE_STREAMS: 1 (or less) = none, the evaluations run on the context's stream; HOP_SPINE_SETS: how many groups can be in flight without a hand-over wait
+  static int env_streams() { int k = DEFAULT_STREAMS; if (const char* e = getenv("HOP_SPINE_STREAMS")) k = atoi(e); return k > MAX_STREAMS ? (int)MAX_STREAMS : k; }
+  static int env_sets() { int k = DEFAULT_SETS; if (const char* e = getenv("HOP_SPINE_SETS")) k = atoi(e); return k < 1 ? 1 : k > MAX_SETS ? (int)MAX_SETS : k; }
+  explicit HipBackend(hop_ctx* ctx, bool sub = false) : c(ctx), arena(nullptr), is_sub_(sub), on_stream_(0), seq_(0), issued_(0) {
     size_t o = 0;
     auto take = [&](size_t bytes) { size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
     o_jobs = take(MAXN * sizeof(hop_rqt_job)); o_syn = take(MAXN * sizeof(hop_cu_syntax)); o_isyn = take(MAXN * sizeof(hop_intra_cu_syntax)); o_isyn_out = take(MAXN * sizeof(hop_intra_cu_syntax));
@@ -240,28 +246,63 @@ class HipBackend : public BatchInner {
     }
   }
   ~HipBackend() {
-    for (auto b : subs_) delete b;
+    for (auto b : sets_) delete b;
     for (auto v : views_) hop_ctx_destroy(v);
+    for (auto s : estreams_) (void)hipStreamDestroy(s);                   // (after the views that borrowed them)
     if (arena) (void)hipFree(arena); if (hin) (void)hipHostFree(hin); if (hout) (void)hipHostFree(hout);
   }
-  // k further streams (views of the context, each with a backend of its own): the candidate evaluations of one round -- SS/GT candidates with and without residual,
-  // intra 2Nx2N, intra NxN: chains that touch different candidate slots -- are issued one per stream and collected in end_round()
-  bool add_streams(int k) {
+  // s evaluation streams and k buffer sets: the candidate evaluations of one round -- SS/GT candidates with and without residual, intra 2Nx2N, intra NxN, of two
+  // adjacent CU sizes: chains that touch different candidate slots -- are issued side by side and collected in end_round().  A set is a view of the context with a
+  // backend of its own (work areas, arena, pinned buffers) that holds one group from its issue to its collection; the view works on whichever of the streams the
+  // group is placed on (issue()).  More sets than streams: a round has up to 7 groups, and none of them should wait for a buffer.
+  bool add_streams(int s, int k) {
+    for (int i = 0; i < s; i++) {
+      hipStream_t st = nullptr;
+      if (hop_view_stream_create(c, &st) != HOP_OK) return false;
+      estreams_.push_back(st);
+    }
     for (int i = 0; i < k; i++) {
       hop_ctx* v = nullptr;
-      if (hop_ctx_create_view(c, &v) != HOP_OK) return false;
+      if (hop_ctx_create_view_on(c, estreams_[i % s], &v) != HOP_OK) return false;
       HipBackend* b = new HipBackend(v, true);
       if (!b->ok()) { delete b; hop_ctx_destroy(v); return false; }
-      views_.push_back(v); subs_.push_back(b);
+      views_.push_back(v); sets_.push_back(b);
     }
     return true;
   }
-  bool can_defer() { return !subs_.empty(); }
+  bool can_defer() { return !sets_.empty(); }
   void end_round() {
-    bool any = false; for (auto b : subs_) any |= (bool)b->collect_;
+    bool any = false; for (auto b : sets_) any |= (bool)b->collect_;
     if (!any) return;
     Tick t(9);                                                            // the wait for the evaluation chains of the round
-    for (auto b : subs_) if (b->collect_) { std::function<void()> f; f.swap(b->collect_); f(); if (b->c->err[0] && !c->err[0]) strncpy(c->err, b->c->err, sizeof(c->err) - 1); }
+    for (auto b : sets_) if (b->collect_) collect_set(b);
+  }
+  // the second half of the group a set holds; the set is free afterwards.  An error text of its chain goes to the owner's context, also when the collection throws
+  void collect_set(HipBackend* b) {
+    std::function<void()> f; f.swap(b->collect_);
+    try { f(); } catch (...) { if (b->c->err[0] && !c->err[0]) strncpy(c->err, b->c->err, sizeof(c->err) - 1); throw; }
+    if (b->c->err[0] && !c->err[0]) strncpy(c->err, b->c->err, sizeof(c->err) - 1);
+  }
+  // a group of one class into a free set, on the stream hop_eval_place names: the one whose uncollected chains are expected to end first.  Only when every set holds
+  // an uncollected group does the host wait here -- for the chain issued longest ago (the hand-over wait of hop_encode_stats)
+  template <class Run>
+  void issue(int kind, int log2_cu, int flag, int n, Run run) {
+    HipBackend* b = nullptr;
+    for (auto q : sets_) if (!q->collect_) { b = q; break; }
+    if (!b) {
+      const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+      for (auto q : sets_) if (!b || q->seq_ < b->seq_) b = q;
+      collect_set(b);
+      const double d = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+      std::lock_guard<std::mutex> g(g_stat_lock); g_stat_ms[STAT_HANDOVER_MS] += d; g_stat_calls[STAT_HANDOVER_CALLS] += 1;
+    }
+    int32_t n_pending[MAX_STREAMS] = { 0 }, pending[MAX_STREAMS * MAX_SETS * 4];
+    for (auto q : sets_) if (q->collect_) { const int s = q->on_stream_; memcpy(pending + (s * MAX_SETS + n_pending[s]++) * 4, q->cls_, sizeof(q->cls_)); }
+    const int32_t cls[4] = { kind, log2_cu, flag, n };
+    const int s = hop_eval_place(cls, (int)estreams_.size(), n_pending, pending, MAX_SETS);
+    hop_view_set_stream(b->c, estreams_[s]);
+    b->on_stream_ = s; memcpy(b->cls_, cls, sizeof(cls)); b->seq_ = ++issued_;
+    run(b);
   }
   bool ok() const { return arena != nullptr; }
 
@@ -353,7 +394,7 @@ class HipBackend : public BatchInner {
   // n candidates of ONE class (CU size; with or without residual)
   void inter_n(int n, const InterEval* const* e, const Coder* const* in, EvalResult* const* out) {
     if (n > MAXN) { for (int o = 0; o < n; o += MAXN) inter_n(n - o < MAXN ? n - o : MAXN, e + o, in + o, out + o); return; }   // larger batches in parts
-    if (!subs_.empty()) { HipBackend* b = subs_[rr_++ % subs_.size()]; if (b->collect_) { std::function<void()> f; f.swap(b->collect_); f(); } b->inter_n(n, e, in, out); return; }
+    if (!sets_.empty()) { issue(HOP_EVAL_INTER, e[0]->job.log2_cu, e[0]->skip_res != 0, n, [&](HipBackend* b) { b->inter_n(n, e, in, out); }); return; }
     on_device();
     Tick t(e[0]->skip_res ? 5 : 4);
     hipStream_t s = c->stream;
@@ -409,7 +450,7 @@ class HipBackend : public BatchInner {
   }
   void intra_n(int n, const IntraEval* const* e, const Coder* const* in, EvalResult* const* out) {
     if (n > MAXN) { for (int o = 0; o < n; o += MAXN) intra_n(n - o < MAXN ? n - o : MAXN, e + o, in + o, out + o); return; }
-    if (!subs_.empty()) { HipBackend* b = subs_[rr_++ % subs_.size()]; if (b->collect_) { std::function<void()> f; f.swap(b->collect_); f(); } b->intra_n(n, e, in, out); return; }
+    if (!sets_.empty()) { issue(HOP_EVAL_INTRA, e[0]->job.log2_cu, e[0]->part_nxn != 0, n, [&](HipBackend* b) { b->intra_n(n, e, in, out); }); return; }
     on_device();
     Tick t(6);
     hipStream_t s = c->stream;
@@ -459,7 +500,9 @@ class HipBackend : public BatchInner {
   }
  private:
   hop_ctx* c; char* arena; size_t bytes; char* hin; char* hout; size_t io_bytes, o_in, o_out;
-  bool is_sub_; int rr_; std::vector<hop_ctx*> views_; std::vector<HipBackend*> subs_; std::function<void()> collect_;   // collect_: the second half of a batch issued on this (sub) backend
+  bool is_sub_; std::function<void()> collect_;                         // collect_: the second half of a batch issued on this (sub) backend, a buffer set of its owner
+  int on_stream_; int32_t cls_[4]; uint64_t seq_;                        // ... and which of the owner's streams it was issued on, its class (hop_eval_place), its number in the order of issue
+  std::vector<hipStream_t> estreams_; std::vector<hop_ctx*> views_; std::vector<HipBackend*> sets_; uint64_t issued_;   // the owner's evaluation streams and buffer sets
   size_t o_jobs, o_syn, o_isyn, o_isyn_out, o_opts, o_sjobs, o_sres, o_res, o_cres, o_coef, o_reco_y, o_reco_c, o_ctx_in, o_cu_in, o_ctx_after, o_ctx_out, o_cu_out, o_fin, o_bits, o_skipped,
          o_cost, o_dist, o_pjobs, o_djobs, o_pout, o_mjobs, o_mres;
 };
@@ -537,9 +580,9 @@ int hop_encode_frame(hop_ctx* c, const hop_enc_params* p, double* ctu_cost, uint
   HipBackend be(c);
   if (!be.ok()) return HOP_ERR_DEVICE;
   if (c->slots > 0 && p->wavefront_lag > 0 && !p->plain_intra) {         // candidates side by side: their evaluation chains of one round on streams of their own
-    int k = 4; if (const char* e = getenv("HOP_SPINE_STREAMS")) k = atoi(e);
+    int k = HipBackend::env_streams();
     if (c->prof_on) k = 1;                                               // profiling (hop_profile_*) records on the context's own stream
-    if (k > 1 && !be.add_streams(k > 8 ? 8 : k)) return hop_set_err(c, HOP_ERR_DEVICE, "hop_encode_frame: could not create the evaluation streams");
+    if (k > 1 && !be.add_streams(k, HipBackend::env_sets())) return hop_set_err(c, HOP_ERR_DEVICE, "hop_encode_frame: could not create the evaluation streams");
   }
   // streams > 1: one view of the context (own stream, own work areas) per CTU row in flight; their launch chains overlap on the device
   std::vector<hop_ctx*> views; std::vector<HipBackend*> vbe; std::vector<Backend*> lanes;
@@ -566,14 +609,14 @@ int hop_encode_frame(hop_ctx* c, const hop_enc_params* p, double* ctu_cost, uint
   std::vector<hop_ctx*> gviews; std::vector<HipBackend*> gbe(1, &be);
   if (G > 1) {
     if (!c->stash) { HIPCHK(c, hipMalloc((void**)&c->stash, (size_t)STASH_SLOTS * STASH_SAMPLES * 2)); c->stash_slots = STASH_SLOTS; }
-    int ks = 4; if (const char* e = getenv("HOP_SPINE_STREAMS")) ks = atoi(e);
+    const int ks = HipBackend::env_streams();
     bool ok = true;
     for (int g = 1; g < G && ok; g++) {
       hop_ctx* v = nullptr;
       if (hop_ctx_create_view(c, &v) != HOP_OK) { ok = false; break; }
       gviews.push_back(v);
       HipBackend* b = new HipBackend(v); gbe.push_back(b);
-      ok = b->ok() && (c->slots <= 0 || p->plain_intra || ks <= 1 || b->add_streams(ks > 8 ? 8 : ks));
+      ok = b->ok() && (c->slots <= 0 || p->plain_intra || ks <= 1 || b->add_streams(ks, HipBackend::env_sets()));
     }
     if (!ok) { for (size_t g = 1; g < gbe.size(); g++) delete gbe[g]; for (auto v : gviews) hop_ctx_destroy(v); return hop_set_err(c, HOP_ERR_DEVICE, "hop_encode_frame: could not create the %d picture groups", G); }
   }

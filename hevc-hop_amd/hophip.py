@@ -187,6 +187,27 @@ def mirror_size(m):
     return m.itemsize if isinstance(m, np.dtype) else ctypes.sizeof(m)
 
 
+HOP_EVAL_INTER, HOP_EVAL_INTRA = 0, 1
+
+
+def eval_expected_ms(L, cls):
+    """hop_eval_expected_ms: the expected length of the chain of an evaluation group of class cls = (kind, log2 CU size, flag, candidates)"""
+    L.hop_eval_expected_ms.argtypes = [ctypes.c_void_p]; L.hop_eval_expected_ms.restype = ctypes.c_double
+    a = np.array(cls, np.int32)
+    return float(L.hop_eval_expected_ms(a.ctypes.data))
+
+
+def eval_place(L, cls, streams, pitch=16):
+    """hop_eval_place: the evaluation stream a new group of class cls is issued on; streams[s] = the classes issued on stream s and not yet collected"""
+    L.hop_eval_place.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]; L.hop_eval_place.restype = ctypes.c_int
+    n_pending = np.array([len(q) for q in streams], np.int32)
+    pending = np.full((len(streams), pitch, 4), -7, np.int32)              # (what lies beyond n_pending[s] is not a class and is not read)
+    for s, q in enumerate(streams):
+        for k, c in enumerate(q): pending[s, k] = c
+    a = np.array(cls, np.int32)
+    return int(L.hop_eval_place(a.ctypes.data, len(streams), n_pending.ctypes.data, pending.ctypes.data, pitch))
+
+
 def load():
     global LIB_PATH
     if os.environ.get("HOP_LIB"): LIB_PATH = os.environ["HOP_LIB"]      # (development: a differently built library)
@@ -667,6 +688,7 @@ class Context:
         self.L.hop_encode_stats(ms, calls)
         names = ("me_search", "pred_inter", "distortion", "valid_pattern", "inter_cu", "inter_cu_skip", "intra_cu", "recon_stash", "commit", "evaluation_wait")
         d = {k: {"ms": ms[i], "calls": int(calls[i])} for i, k in enumerate(names)}
+        d["evaluation_handover"] = {"ms": ms[15], "calls": int(calls[13])}   # evaluation groups that waited for an earlier chain's end before they could be issued
         d["rendezvous"] = {"rounds": int(calls[14]), "requests": int(calls[15]), "serve_ms": float(ms[14]), "run_ms": float(ms[13]),
                            "searches_reaching_below": int(calls[10]), "first_ctu_reaching_below": int(ms[10]), "searches_reaching_above": int(calls[11]), "first_ctu_reaching_above": int(ms[11]),
                            "waits": int(calls[12]), "wait_ms": float(ms[12])}

@@ -75,6 +75,37 @@ int hop_me_reach_above(int pic_w, const hop_pu_job* job, int row_top) {
   return imin(x, pic_w - 1) >> 6;
 }
 
+// ---- where an evaluation group of hop_encode_frame goes (csrc/k_spine.hip: S evaluation streams, a round's groups dealt to them) ----
+// A class is four ints: kind (HOP_EVAL_INTER / HOP_EVAL_INTRA), log2 of the CU size (3..6), flag (inter: the candidates carry no residual; intra: NxN), candidates.
+// Expected length of a class's chain on a stream of its own, in ms.  The walks (rows 0, 2, 3) are the HIP-event times per launch of the profiled pass of
+// `bench.py --gpus 1 --steps 2 --warmup 0 --full --no-cpu --views 0` on an MI355X (its `kernels`, profile ids 12 - 20: 1024x64 of the bench's frame, 48 slots); the
+// chain without residual (row 1) is not among those ids: four short launches (prediction, k_cu_skip, levels, copies: about 10 us each in the bench's kernel trace).
+// The candidates of a group are workgroups side by side, one walk each, so a group is as long as its longest walk until the device is full; n counts only as the number of
+// such fills.  The size of a fill, 1024 candidates (256 compute units x 4 workgroups), is reasoned from the walks' occupancy, NOT measured: the groups of the
+// bench hold tens of candidates, a group holds at most 2048, so the rule has never decided a placement.  Row 1 is an estimate too.  The table places groups, it decides nothing else: the results do not depend on it.
+static const double k_eval_ms[4][4] = {            // CU 8, 16, 32, 64
+  { 0.325, 1.779, 5.540, 14.346 },                 // SS/GT candidates with residual (k_inter_walk)
+  { 0.05, 0.05, 0.06, 0.08 },                      // ... without
+  { 0.522, 1.794, 5.502, 17.433 },                 // intra 2Nx2N (k_iw_*)
+  { 0.722, 0.722, 0.722, 0.722 },                  // intra NxN (8x8 CUs only)
+};
+double hop_eval_expected_ms(const int32_t cls[4]) {
+  const int size = cls[1] < 3 ? 0 : cls[1] > 6 ? 3 : cls[1] - 3, row = (cls[0] == HOP_EVAL_INTRA ? 2 : 0) + (cls[2] ? 1 : 0), fills = cls[3] > 1024 ? (cls[3] + 1023) / 1024 : 1;
+  return k_eval_ms[row][size] * fills;
+}
+// The stream, of n_streams, for a new group of class cls: the one whose chains issued and not yet collected -- n_pending[s] classes at pending + (s * pitch) * 4 --
+// add up to the smallest expected time; of equals the lowest index.  Groups are placed as they arrive: greedy, not optimal.
+int hop_eval_place(const int32_t cls[4], int n_streams, const int32_t* n_pending, const int32_t* pending, int pitch) {
+  (void)cls;                                                             // part of the interface only: every stream runs every class at the same speed, so the new group's own length does not choose
+  int best = 0; double best_ms = 0.0;
+  for (int s = 0; s < n_streams; s++) {
+    double ms = 0.0;
+    for (int k = 0; k < n_pending[s]; k++) ms += hop_eval_expected_ms(pending + ((size_t)s * pitch + k) * 4);
+    if (s == 0 || ms < best_ms) { best = s; best_ms = ms; }
+  }
+  return best;
+}
+
 uint32_t hop_component_bits(int v) { return hl_component_bits(v); }
 uint32_t hop_bits_gt(const int v[8]) {   // IT_GT_AFFINE: corners 0..2 only, TComRdCost.h:205-215
   uint32_t b = 0; for (int i = 0; i < 6; i++) b += hl_component_bits(v[i]); return b;

@@ -165,6 +165,15 @@ uint32_t hop_component_bits(int v);
  * What a row of hop_encode_frame's exact wavefront (hop_encode_set_exact) waits for before the search: the row above must have retired that column. */
 int hop_me_reach_above(int pic_w, const hop_pu_job* job, int row_top);
 uint32_t hop_bits_gt(const int v[8]);
+/* Where hop_encode_frame issues a group of candidate evaluations (one launch chain per kind and CU-size class of a round): it has HOP_SPINE_STREAMS evaluation
+ * streams, and a new group goes to the one whose chains issued and not yet collected add up to the smallest expected time (ties: the lowest index).  A class is
+ * int32_t[4] = { kind, log2 of the CU size (3..6), flag (HOP_EVAL_INTER: the candidates carry no residual; HOP_EVAL_INTRA: NxN), candidates }.
+ * hop_eval_expected_ms: the expected length of a class's chain from the table in host/hop_hostlogic.cpp.  hop_eval_place: n_pending[s] classes of stream s lie at
+ * pending + (s * pitch) * 4.  Pure functions; the results of an encode do not depend on them. */
+#define HOP_EVAL_INTER 0
+#define HOP_EVAL_INTRA 1
+double hop_eval_expected_ms(const int32_t cls[4]);
+int hop_eval_place(const int32_t cls[4], int n_streams, const int32_t* n_pending, const int32_t* pending, int pitch);
 /* replaces: the bits/cost bookkeeping at the tail of xMotionEstimation (TEncSearch.cpp:4654-4682):
  * folds one hop_pu_result into (mv quarter-pel, bits, cost); bits_in = ruiBits on entry. */
 void hop_me_finish(const hop_pu_job* job, const hop_pu_result* res, int stage, uint32_t bits_in,
