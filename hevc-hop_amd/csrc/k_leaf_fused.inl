@@ -30,12 +30,15 @@ template <class SH, int MAXLOG2>
 __device__ __noinline__ static void leaf_serial(SH* Lg, const int j, const int LOG2, const hop_tu_rd_job* jobs, const int n, const hop_cabac_ctx* ctx_in, const int64_t* coef_off,
                                                 uint32_t* as, unsigned long long* fr, hop_rdoq_job* rq, hop_coeff_bits_job* cb, char* work) {
   SH& L = *hopd_lds(Lg);
+  WS(HOP_WS_LEAF_ESTBITS);
   turd_setup_body(j, jobs, n, ctx_in, coef_off, L.ebits, &L.eb, rq, cb, L.ctx);
+  WS(HOP_WS_LEAF_RDOQ);
   const hop_rdoq_job rj = rq[j];
   if (LOG2 == 2) rdoq_tu<2>(rj, &L.eb, L.scan, L.scanCG, L.cgSig, 1, L.src, L.lev, as + j, L.work, 1, 0);
   else if (MAXLOG2 == 3 || LOG2 == 3) rdoq_tu<3>(rj, &L.eb, L.scan, L.scanCG, L.cgSig, 1, L.src, L.lev, as + j, L.work, 1, 0);
   else if (LOG2 == 4) rdoq_tu<4>(rj, &L.eb, L.scan, L.scanCG, L.cgSig, 1, L.src, L.lev, as + j, L.work, 1, 0);
   else rdoq_tu<5>(rj, &L.eb, L.scan, L.scanCG, L.cgSig, 1, L.src, L.lev, as + j, (double*)(work + (size_t)j * LEAF_WORK_PER_TU), 1, 0);
+  WS(HOP_WS_LEAF_BITS);
   const hop_coeff_bits_job bj = cb[j];
   fr[j] = cb_code_tu_at(L.cab, 0, L.lev, bj.log2_size, bj.comp != 0, bj.scan_idx, bj.sign_hide, bj.use_ts, bj.ts_flag, bj.cbf_ctx_plus1, L.scan, L.scanCG);
 }
@@ -50,6 +53,7 @@ __device__ static void turd_fused_body(LeafShared& L_, const int j, const hop_tu
   if (jb.log2_size < 2 || jb.log2_size > 5) return;                   // an empty slot of a job table (k_rqt.inl); uniform over the workgroup
   const bool small = jb.log2_size <= 3;
   const int LOG2 = jb.log2_size, N2 = 1 << (2 * LOG2), CGN = N2 >> 4;
+  WS(HOP_WS_LEAF_FORWARD);
   // residual, forward transform (or the transform-skip scaling), distortion of the zero block
   if (small) { if (tid < 64) turd_forward_small_body(L.t.small, 0, tid, j, jobs, n, pic, coef_off, coef, zs); }
   else turd_forward_body(L.t.big, j, jobs, pic, coef_off, coef, zs);
@@ -64,7 +68,9 @@ __device__ static void turd_fused_body(LeafShared& L_, const int j, const hop_tu
   for (int i = tid; i < 128; i += 256) L.ebits[i] = entropy_bits[i];
   __syncthreads();
   if (tid == 0) leaf_serial<LeafShared, 5>(&L, j, LOG2, jobs, n, ctx_in, coef_off, as, fr, rq, cb, work);   // the serial stages
+  WS(HOP_WS_LEAF_WAIT);
   __syncthreads();
+  WS(HOP_WS_LEAF_INVERSE);
   for (int i = tid; i < N2; i += 256) levels[off + i] = L.lev[i];
   __threadfence_block();
   __syncthreads();
@@ -73,6 +79,7 @@ __device__ static void turd_fused_body(LeafShared& L_, const int j, const hop_tu
   else turd_inverse_body(L.t.big, j, jobs, pic, coef_off, levels, as, ns, rec_y, rec_cb, rec_cr);
   __threadfence_block();
   __syncthreads();
+  WS(HOP_WS_LEAF_DECIDE);
   if (tid == 0) turd_decide_body(j, jobs, n, ctx_in, coef_off, entropy_bits, as, fr, zs, ns, levels, res);
 }
 __global__ __launch_bounds__(256) void k_turd_fused(const hop_tu_rd_job* __restrict__ jobs, int n, hop_pics pic, const hop_cabac_ctx* __restrict__ ctx_in,
@@ -103,6 +110,7 @@ __device__ static __forceinline__ void turd_fused_small_wave_body(LeafSmallShare
   const bool live = j >= 0 && jb.log2_size >= 2 && jb.log2_size <= 3;      // (uniform over the wave)
   const int LOG2 = live ? jb.log2_size : 2, N2 = 1 << (2 * LOG2), CGN = N2 >> 4;
   int64_t off = 0;
+  WS(HOP_WS_LEAF_FORWARD);
   if (live) {
     turd_forward_small_body(L.t, 0, lane, j, jobs, n, pic, coef_off, coef, zs);
     const uint16_t* s0 = rq_scan(scans, jb.scan_idx, LOG2); const uint16_t* s1 = rq_scan_cg(scans, jb.scan_idx, LOG2);
@@ -119,13 +127,16 @@ __device__ static __forceinline__ void turd_fused_small_wave_body(LeafSmallShare
   }
   __syncthreads();
   if (live && lane == 0) leaf_serial<LeafSmallShared, 3>(&L, j, LOG2, jobs, n, ctx_in, coef_off, as, fr, rq, cb, nullptr);
+  WS(HOP_WS_LEAF_WAIT);                                                 // (thread 0's own unit is done, or it had none: the other waves' serial lanes)
   __syncthreads();
+  WS(HOP_WS_LEAF_INVERSE);
   if (live && lane < N2) levels[off + lane] = L.lev[lane];
   __threadfence_block();
   __syncthreads();
   if (live) turd_inverse_small_body(L.t, 0, lane, j, jobs, n, pic, coef_off, levels, as, ns, rec_y, rec_cb, rec_cr);
   __threadfence_block();
   __syncthreads();
+  WS_IF(live, HOP_WS_LEAF_DECIDE);
   if (live && lane == 0) turd_decide_body(j, jobs, n, ctx_in, coef_off, entropy_bits, as, fr, zs, ns, levels, res);
 }
 

@@ -120,6 +120,7 @@ __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_inter_walk(InterWa
   __shared__ InterLeafShared IL;
   LeafShared& L = IL.u.big;
   __shared__ CabacLds1 sh1;
+  WS_BEGIN();
   walk_tables_fill(A.scans);                                             // the one-lane coders' bin table and the scan tables into LDS: all threads, first thing, the barrier inside
   const int i = blockIdx.x, tid = threadIdx.x;
   const RqtClass k = A.k;
@@ -138,13 +139,16 @@ __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_inter_walk(InterWa
       // moment, so every candidate owns three fixed slots of the job / result / scratch tables: the tables are handed to the bodies shifted so that their index lands there
       const int ncomp = nd.code_chroma ? 3 : 1, nts = nd.ts_y + 2 * nd.ts_c;
       const ptrdiff_t sh_c = (ptrdiff_t)(3 - ncomp) * i, sh_t = (ptrdiff_t)(3 - nts) * i;
+      WS(HOP_WS_NODE_BEGIN);
       if (tid == 0) rqt_begin_body(i, k, nd, A.jobs, A.bd_y, A.bd_c, A.cur, A.root[d], A.res, A.work, A.tuj + sh_c, A.off + sh_c, A.tuj2 + sh_t, A.off2 + sh_t, A.ts_base);
       __syncthreads();
       if (nd.check_full) {
         walk_inter_leaves(A, IL, i, d, ncomp, nts);
+        WS(HOP_WS_NODE_SINGLE);
         if (tid == 0) rqt_single_body(sh1, 0, i, k, nd, A.jobs, A.cur, A.root[d], A.test[d], A.res, A.work, A.tr + sh_c, A.tr2 + sh_t, A.coef, A.ts_base, s_scan_tables);
         __syncthreads();
       }
+      WS(HOP_WS_OTHER);
       if (!nd.check_split) { sp--; continue; }
       s_child[sp] = 0;
     }
@@ -154,10 +158,13 @@ __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_inter_walk(InterWa
       sp++;
       continue;
     }
+    WS(HOP_WS_NODE_CLOSE);
     if (tid == 0) rqt_close_body(sh1, 0, i, k, nd, A.jobs, A.cur, A.root[d], A.test[d], A.res, A.work, A.coef, s_scan_tables);
     __syncthreads();
+    WS(HOP_WS_OTHER);
     sp--;
   }
+  WS(HOP_WS_TAIL);
   rqt_final_body(i, tid, 256, k, A.work, A.res, A.coef, A.coef_out, A.cur, A.ctx_after);
   __syncthreads();
   // ---- the wrapper's tail: root-cbf-zero test, the reconstruction and its distortion ----
@@ -170,9 +177,11 @@ __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_inter_walk(InterWa
   if (tid == 0) {
     fin_sum_body(i, A.jobs, A.nj, A.ftuj, A.fsse, A.fin);
     // ---- the CU's syntax bits from the CI_CURR_BEST state, the cost ----
+    WS(HOP_WS_CU_BITS);
     cu_bits_body(sh1, 0, i, k, A.jobs, A.syn, A.res, A.coef_out, A.ctx_in, A.cu_in, A.bits, A.skipped, A.ctx_out, A.cu_out, s_scan_tables);
     A.cost[i] = rqt_cost(A.bits[i], A.fin[i].dist[0] + A.fin[i].dist[1] + A.fin[i].dist[2], A.jobs[i].lambda_rd);
   }
+  WS_END(HOP_WSK_INTER_WALK, k.log2_cu, 0);
 }
 
 // HOP_WALK_FILL=<0..255> (developer switch, read per call): the walk launchers fill their work buffer with that byte, on the context's stream, before the launch.  Every word
@@ -291,6 +300,7 @@ __device__ static __forceinline__ void walk_intra_rqt(const IntraWalk& A, const 
   const int tid = threadIdx.x;
   const RqtClass k = A.k;
   const int parts = 1 << (2 * (k.log2_cu - 2)), pitch = W.pic.pic_w;
+  WS(HOP_WS_OTHER);
   if (tid == 0) irqt_init_body(i, W.jobs, A.ctx_in, A.cu_in, A.cur, A.cucur, A.irwork, W.tmp);
   __syncthreads();
   int s_rel[4], s_child[4];
@@ -303,24 +313,29 @@ __device__ static __forceinline__ void walk_intra_rqt(const IntraWalk& A, const 
     nd.check_split = log2 > k.log2_min_tu && !(check_first && nd.check_full);
     nd.ts_y = (k.use_ts && nd.check_full && log2 == 2) ? 1 : 0;
     if (s_child[sp] < 0) {
+      WS(HOP_WS_NODE_BEGIN);
       if (tid == 0) irqt_begin_body(i, k, nd, W.jobs, W.syn, W.opt, A.bd_y, A.cur, A.cucur, A.root[d], A.curoot[d], W.tmp, A.irwork, A.pj, A.modes, A.tuj, A.off, A.tuj2, A.off2, A.ts_base, nullptr);
       __syncthreads();
       if (nd.check_full) {
+        WS(HOP_WS_PREDICT);
         intra_pred_body(L.intra, A.pj + i, A.modes[i], W.pic, W.rec_y);
         __syncthreads();
         if (nd.ts_y) {
           IW_LEAF(A.tuj2, A.root[d], A.off2, A.coef, A.tr2);
           __syncthreads();
+          WS(HOP_WS_COPY);
           irqt_copy_body(i, tid, 256, 1, k, nd, W.jobs, W.syn, A.irwork, W.rec_y, pitch, A.recl, A.park, nullptr);
           __syncthreads();
         }
         IW_LEAF(A.tuj, A.root[d], A.off, A.coef, A.tr);
         __syncthreads();
-        if (nd.check_split) { irqt_copy_body(i, tid, 256, 0, k, nd, W.jobs, W.syn, A.irwork, W.rec_y, pitch, A.recl, A.park, nullptr); __syncthreads(); }
+        if (nd.check_split) { WS(HOP_WS_COPY); irqt_copy_body(i, tid, 256, 0, k, nd, W.jobs, W.syn, A.irwork, W.rec_y, pitch, A.recl, A.park, nullptr); __syncthreads(); }
+        WS(HOP_WS_NODE_SINGLE);
         if (tid == 0) irqt_single_body(sh1, 0, i, k, nd, W.jobs, W.syn, W.opt, A.cur, A.cucur, A.root[d], A.curoot[d], A.test[d], A.cutest[d], W.tmp, A.irwork, A.tr, A.tr2, A.coef, A.ts_base,
                                        W.rec_y, pitch, A.park, s_scan_tables, nullptr);
         __syncthreads();
       }
+      WS(HOP_WS_OTHER);
       if (!nd.check_split) { sp--; continue; }
       s_child[sp] = 0;
     }
@@ -330,11 +345,14 @@ __device__ static __forceinline__ void walk_intra_rqt(const IntraWalk& A, const 
       sp++;
       continue;
     }
+    WS(HOP_WS_NODE_CLOSE);
     if (tid == 0) irqt_close_body(sh1, 0, i, k, nd, W.jobs, W.syn, A.cur, A.cucur, A.root[d], A.curoot[d], A.test[d], A.cutest[d], W.tmp, A.irwork, A.coef, s_scan_tables, nullptr);
     __syncthreads();
-    if (nd.check_full) { irqt_copy_body(i, tid, 256, 2, k, nd, W.jobs, W.syn, A.irwork, W.rec_y, pitch, A.recl, A.park, nullptr); __syncthreads(); }
+    if (nd.check_full) { WS(HOP_WS_COPY); irqt_copy_body(i, tid, 256, 2, k, nd, W.jobs, W.syn, A.irwork, W.rec_y, pitch, A.recl, A.park, nullptr); __syncthreads(); }
+    WS(HOP_WS_OTHER);
     sp--;
   }
+  WS(HOP_WS_TAIL);
   irqt_final_body(i, tid, 256, k, tr_depth0, W.syn, A.irwork, W.tmp, A.coef, W.coef_tmp, A.cur, A.cucur, nullptr, nullptr, nullptr);
   __syncthreads();
 }
@@ -342,10 +360,13 @@ __device__ static __forceinline__ void walk_intra_rqt(const IntraWalk& A, const 
 // ---- the phases of an intra candidate, each on the whole workgroup, index i into the arrays of A ----
 // estIntraPredQT of PU pu up to the candidate list (:2430-2493)
 __device__ static __forceinline__ void iw_luma_prep(const IntraWalk& A, WalkShared& L, const int i, const int pu) {
+  WS(HOP_WS_NODE_BEGIN);
   if (threadIdx.x == 0) is_prep_body(i, A.k, pu, A.nxn, A.jobs, A.sj, A.opt, A.ctx_in, A.cu_in, A.sres, A.syn, A.rj, A.mj, A.iswork);
   __syncthreads();
+  WS(HOP_WS_PREDICT);
   intra_rough_body(L.intra, A.rj + i, A.pic, A.rec_y, A.satd + (size_t)i * 35);
   __syncthreads();
+  WS(HOP_WS_OTHER);                                                      // (the candidate list)
   if (threadIdx.x == 0) intra_modes_body<true>(i, A.mj, A.satd, A.mres);
   __syncthreads();
 }
@@ -354,13 +375,16 @@ __device__ static __forceinline__ void iw_luma_prep(const IntraWalk& A, WalkShar
 __device__ static __forceinline__ void iw_luma_final(const IntraWalk& A, WalkShared& L, CabacLds1& sh1, const int i, const int pu) {
   const int tid = threadIdx.x, n_max = A.num_full_rd + 2, pitch = A.pic.pic_w;
   const bool skip = !A.final_always && rqt_intra_final_repeats(A.k, A.nxn);
+  WS(HOP_WS_TAIL);
   if (tid == 0) is_pick_body(i, pu, n_max, n_max, A.mres, A.iswork, A.syn, A.active);
   __syncthreads();
   if (!skip) {
     walk_intra_rqt(A, iw_view(A), L, sh1, i, A.nxn, 0);
+    WS(HOP_WS_COPY);
     is_keep_body(i, tid, 256, A.k, pu, A.nxn, n_max, n_max, A.jobs, A.mres, A.syn, A.tmp, A.coef_tmp, A.rec_y, pitch, A.iswork, A.coef_out, A.reco_y);
     __syncthreads();
   }
+  WS(HOP_WS_TAIL);
   is_commit_body(i, tid, 256, A.k, pu, A.nxn, skip ? 1 : 0, A.jobs, A.iswork, A.mres, A.syn, A.res, A.sres, A.rec_y, pitch, A.reco_y);
   __syncthreads();
 }
@@ -371,6 +395,7 @@ __device__ static __forceinline__ void iw_chroma_mode(const IntraWalk& A, const 
   const RqtClass k = A.k;
   const int parts = 1 << (2 * (k.log2_cu - 2)), pitch_c = W.pic.pic_w >> 1;
   const hop_rqt_result* r = W.res + i;
+  WS(HOP_WS_OTHER);
   if (tid == 0) ic_mode_body(i, m, W.jobs, A.ctx_in, A.ccur, W.csyn, A.icwork);
   __syncthreads();
   int s_part[4], s_child[4];
@@ -384,9 +409,11 @@ __device__ static __forceinline__ void iw_chroma_mode(const IntraWalk& A, const 
       if (tr == d && log2 <= k.log2_max_tu && !(log2 == 2 && (part & 3))) {       // a transform unit of this CU sits here (ic_leaf_here)
         const bool may_ts = k.use_ts && log2 <= 3;
         for (int comp = 1; comp <= 2; comp++) {
+          WS(HOP_WS_NODE_BEGIN);
           if (tid == 0) ic_begin_body(i, k, nd, comp, W.jobs, W.csyn, W.opt, A.bd_c, A.ccur, A.croot, W.res, A.icwork, A.pj, A.modes, A.tuj, A.off, A.tuj2, A.off2, A.ts_base);
           __syncthreads();
           if (comp == 1) {
+            WS(HOP_WS_PREDICT);
             intra_pred_chroma_body(L.intra, A.pj + i, A.modes[i], 1, W.pic, W.rec_cb, W.rec_cr);
             __syncthreads();
             intra_pred_chroma_body(L.intra, A.pj + i, A.modes[i], 2, W.pic, W.rec_cb, W.rec_cr);
@@ -396,13 +423,16 @@ __device__ static __forceinline__ void iw_chroma_mode(const IntraWalk& A, const 
           if (may_ts) {
             IW_LEAF(A.tuj2, A.ccur, A.off2, A.ccoef, A.tr2);
             __syncthreads();
+            WS(HOP_WS_COPY);
             if (tid < 16) ic_park_body(i, tid, k, nd, W.jobs, W.opt, W.res, recc, pitch_c, A.cpark);
             __syncthreads();
           }
           IW_LEAF(A.tuj, A.ccur, A.off, A.ccoef, A.tr);
           __syncthreads();
+          WS(HOP_WS_NODE_SINGLE);
           if (tid == 0) ic_single_body(sh1, 0, i, k, nd, comp, W.jobs, W.csyn, W.opt, A.ccur, A.croot, W.res, A.icwork, A.tr, A.tr2, A.ccoef, A.ts_base, recc, pitch_c, A.cpark, s_scan_tables);
           __syncthreads();
+          WS(HOP_WS_OTHER);
         }
       }
       if (!(tr > d && log2 > k.log2_min_tu)) { sp--; continue; }                   // the tree goes no deeper here
@@ -414,10 +444,13 @@ __device__ static __forceinline__ void iw_chroma_mode(const IntraWalk& A, const 
       sp++;
       continue;
     }
+    WS(HOP_WS_NODE_CLOSE);
     if (tid == 0) ic_fold_body(i, k, nd, W.res);
     __syncthreads();
+    WS(HOP_WS_OTHER);
     sp--;
   }
+  WS(HOP_WS_CU_BITS);
   if (tid == 0) ic_bits_body(sh1, 0, i, k, W.jobs, W.csyn, A.ctx_in, A.cu_in, W.res, A.icwork, A.ccoef, s_scan_tables);
   __syncthreads();
 }
@@ -432,6 +465,7 @@ __device__ static inline void iw_total(const IntraWalk& A, CabacLds1& sh1, const
   if (threadIdx.x == 0) {
     const RqtClass k = A.k;                                              // (a copy: a reference into A handed to a function of its own would put the whole table on the stack)
     A.dist[i] = A.sres[i].dist + A.cres[i].dist;
+    WS(HOP_WS_CU_BITS);
     intra_cu_total_body(sh1, 0, i, k, A.jobs, A.syn_out, A.res, A.coef_out, A.ctx_in, A.cu_in, A.dist, A.bits, A.cost, A.ctx_out, A.cu_out, s_scan_tables);
   }
 }
@@ -440,6 +474,7 @@ __device__ static inline void iw_total(const IntraWalk& A, CabacLds1& sh1, const
 __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_intra_walk(IntraWalk A) {
   __shared__ WalkShared L;
   __shared__ CabacLds1 sh1;
+  WS_BEGIN();
   walk_tables_fill(A.scans);
   const int i = blockIdx.x, tid = threadIdx.x;
   const RqtClass k = A.k;
@@ -451,26 +486,32 @@ __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_intra_walk(IntraWa
   for (int pu = 0; pu < npu; pu++) {
     iw_luma_prep(A, L, i, pu);
     for (int pass = 0; pass < n_max; pass++) {
+      WS(HOP_WS_TAIL);
       if (tid == 0) is_pick_body(i, pu, pass, n_max, A.mres, A.iswork, A.syn, A.active);
       __syncthreads();
       if (!A.active[i]) continue;                                        // this CU's list is shorter (uniform over the workgroup)
       walk_intra_rqt(A, iw_view(A), L, sh1, i, A.nxn, 1);
+      WS(HOP_WS_COPY);
       is_keep_body(i, tid, 256, k, pu, A.nxn, pass, n_max, A.jobs, A.mres, A.syn, A.tmp, A.coef_tmp, A.rec_y, pitch, A.iswork, A.coef_out, A.reco_y);
       __syncthreads();
     }
     iw_luma_final(A, L, sh1, i, pu);
   }
+  WS(HOP_WS_OTHER);
   if (tid == 0) { A.syn_out[i] = A.syn[i]; A.csyn[i] = A.syn[i]; }
   iw_zero_ccoef(A, i);
   __syncthreads();
   for (int m = 0; m < 5; m++) {
     iw_chroma_mode(A, iw_view(A), L, sh1, i, m);
+    WS(HOP_WS_COPY);
     ic_keep_body(i, tid, 256, k, A.jobs, A.res, A.icwork, A.ccoef, A.rec_cb, A.rec_cr, pitch_c, A.coef_out, A.reco_c);
     __syncthreads();
   }
+  WS(HOP_WS_TAIL);
   ic_commit_body(i, tid, 256, k, A.icwork, A.res, A.cres, A.syn_out);
   __syncthreads();
   iw_total(A, sh1, i);
+  WS_END(HOP_WSK_INTRA_WALK, k.log2_cu, A.nxn);
 }
 
 // ---- the candidate passes side by side: k_iw_begin -> per PU (k_iw_cand over (CU, pass) -> k_iw_pick) -> k_iw_chroma over (CU, direction) -> k_iw_finish ----
@@ -500,22 +541,26 @@ __device__ static inline IwView iw_virtual(const IntraWalk& A, const int v, cons
 
 __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_iw_begin(IntraWalk A) {
   __shared__ WalkShared L;
+  WS_BEGIN();
   cab_bin_fill();                                                        // (intra_modes_body reads the bin table; no transform unit is coded here)
   const int i = blockIdx.x, tid = threadIdx.x;
   if (tid == 0) A.syn[i] = A.syn_in[i];
   { uint32_t* z = (uint32_t*)(A.res + i); for (int e = tid; e < (int)(sizeof(hop_rqt_result) / 4); e += 256) z[e] = 0; }
   __syncthreads();
   iw_luma_prep(A, L, i, 0);
+  WS_END(HOP_WSK_IW_BEGIN, A.k.log2_cu, A.nxn);
 }
 
 // grid (n, P): candidate `pass` of PU pu of CU i with bCheckFirst (:2507-2553), in a band of its own; the result stays in vtmp / vcoef_tmp / the band
 __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_iw_cand(IntraWalk A, int pu) {
   __shared__ WalkShared L;
   __shared__ CabacLds1 sh1;
+  WS_BEGIN();
   walk_tables_fill(A.scans);                                             // (before the return of a pass this CU's list does not have)
   const int i = blockIdx.x, pass = blockIdx.y, tid = threadIdx.x;
   const int cnt = (int)A.mres[i].n, n_max = A.num_full_rd + 2;
-  if (pass >= cnt || pass >= n_max) return;
+  if (pass >= cnt || pass >= n_max) return;                              // (a workgroup without a pass leaves no row in the stamps' table)
+  WS(HOP_WS_COPY);
   const int v = i * A.P + pass;
   const hop_rqt_job jb = A.jobs[i];
   if (tid == 0) { A.vjobs[v] = jb; hop_intra_cu_syntax y = A.syn[i]; y.luma_dir[pu] = (int)A.mres[i].modes[pass]; A.vsyn[v] = y; }
@@ -525,6 +570,7 @@ __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_iw_cand(IntraWalk 
   iw_band_prepare(A.rec_y, B.rec_y, A.pic.pic_w, A.pic.pic_w, A.pic_h, jb.x + rqt_zx(part), jb.y + rqt_zy(part), N);
   __syncthreads();
   walk_intra_rqt(A, B, L, sh1, v, A.nxn, 1);
+  WS_END(HOP_WSK_IW_CAND, A.k.log2_cu, A.nxn);
 }
 
 // the decisions over the candidate passes in their order (strict '<': the first of equal costs stays), the winner's arrays, levels and block kept (xSetIntraResultQT), then
@@ -533,17 +579,20 @@ __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_iw_pick(IntraWalk 
   __shared__ WalkShared L;
   __shared__ CabacLds1 sh1;
   __shared__ int s_best;
+  WS_BEGIN();
   walk_tables_fill(A.scans);
   const int i = blockIdx.x, tid = threadIdx.x;
   const RqtClass k = A.k;
   const int n_max = A.num_full_rd + 2, npu = A.nxn ? 4 : 1;
   const int cnt = min((int)A.mres[i].n, n_max);
+  WS(HOP_WS_TAIL);
   if (tid == 0) {
     int best = 0; double bc = 1.7e+308;
     for (int p = 0; p < cnt; p++) { const double c = A.vtmp[i * A.P + p].cost; if (c < bc) { bc = c; best = p; } }
     s_best = best;
   }
   __syncthreads();
+  WS(HOP_WS_COPY);
   {
     const int v = i * A.P + s_best;
     const hop_rqt_job jb = A.jobs[i];
@@ -560,16 +609,19 @@ __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_iw_pick(IntraWalk 
     __syncthreads();
   }
   iw_luma_final(A, L, sh1, i, pu);
-  if (pu + 1 < npu) { iw_luma_prep(A, L, i, pu + 1); return; }
+  if (pu + 1 < npu) { iw_luma_prep(A, L, i, pu + 1); WS_END(HOP_WSK_IW_PICK, k.log2_cu, A.nxn); return; }
   if (tid == 0) A.syn_out[i] = A.syn[i];
+  WS_END(HOP_WSK_IW_PICK, k.log2_cu, A.nxn);
 }
 
 // grid (n, 5): direction m of the chroma search of CU i in bands of its own (both chroma planes), on a copy of the CU's arrays
 __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_iw_chroma(IntraWalk A) {
   __shared__ WalkShared L;
   __shared__ CabacLds1 sh1;
+  WS_BEGIN();
   walk_tables_fill(A.scans);
   const int i = blockIdx.x, m = blockIdx.y, tid = threadIdx.x;
+  WS(HOP_WS_COPY);
   const int v = i * A.P + m;
   const hop_rqt_job jb = A.jobs[i];
   if (tid == 0) { A.vjobs[v] = jb; A.vsyn[v] = A.syn_out[i]; }
@@ -579,25 +631,30 @@ __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_iw_chroma(IntraWal
   const int cu = 1 << A.k.log2_cu, pw = A.pic.pic_w >> 1;
   iw_band_prepare(A.rec_cb, B.rec_cb, pw, pw, A.pic_h >> 1, jb.x >> 1, jb.y >> 1, cu >> 1);
   iw_band_prepare(A.rec_cr, B.rec_cr, pw, pw, A.pic_h >> 1, jb.x >> 1, jb.y >> 1, cu >> 1);
+  WS(HOP_WS_OTHER);
   iw_zero_ccoef(A, v);
   if (tid == 0) A.icwork[v].best_cost = 1.7e+308;                           // (a private record per direction: ic_bits_body leaves this direction's cost there)
   __syncthreads();
   iw_chroma_mode(A, B, L, sh1, v, m);                                         // (ic_mode_body resets the best cost for m == 0 only: the comparison below reads icwork[v].dist / the cost it forms)
+  WS_END(HOP_WSK_IW_CHROMA, A.k.log2_cu, A.nxn);
 }
 
 // the decisions over the five directions in their order, xSetIntraResultChromaQT for the winner, the CU's totals
 __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_iw_finish(IntraWalk A) {
   __shared__ CabacLds1 sh1;
   __shared__ int s_best;
+  WS_BEGIN();
   walk_tables_fill(A.scans);
   const int i = blockIdx.x, tid = threadIdx.x;
   const RqtClass k = A.k;
+  WS(HOP_WS_TAIL);
   if (tid == 0) {
     int best = 0; double bc = 1.7e+308;
     for (int m = 0; m < 5; m++) { const double c = A.icwork[i * A.P + m].best_cost; if (c < bc) { bc = c; best = m; } }
     s_best = best;
   }
   __syncthreads();
+  WS(HOP_WS_COPY);
   const int v = i * A.P + s_best;
   const hop_rqt_job jb = A.jobs[i];
   const IwView B = iw_virtual(A, v, jb.y);
@@ -619,6 +676,7 @@ __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_iw_finish(IntraWal
     const int16_t* last = A.band_rec[comp] + o4; int16_t* out = comp == 1 ? A.rec_cb : A.rec_cr;
     for (int e = tid; e < (int)h2; e += 256) { const int rr = e / half, cc = e % half; out[op + (ptrdiff_t)rr * pitch_c + cc] = last[(ptrdiff_t)rr * pitch_c + cc]; }
   }
+  WS(HOP_WS_TAIL);
   if (tid == 0) {
     const IcWork* w = A.icwork + v;
     A.cres[i].best_mode = w->mode; A.cres[i].dist = w->dist;
@@ -626,6 +684,7 @@ __global__ __launch_bounds__(256, WALK_WAVES_PER_SIMD) void k_iw_finish(IntraWal
   }
   __syncthreads();
   iw_total(A, sh1, i);
+  WS_END(HOP_WSK_IW_FINISH, k.log2_cu, A.nxn);
 }
 
 // candidates side by side (k_iw_*) unless HOP_WALK_CAND=0 or the bands would not fit the budget: P passes per candidate CU

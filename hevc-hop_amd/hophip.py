@@ -11,9 +11,10 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libhophip.so")
+STAMPS_LIB_PATH = os.path.join(HERE, "libhophip_stamps.so")      # the diagnostic build with the walks' stage stamps: HOP_LIB=<this> (Context.walk_stamps)
 
 HOP_STAGE_INT, HOP_STAGE_FRAC, HOP_STAGE_GT = 1, 2, 3
-HOP_ERR_ARG = -1
+HOP_ERR_ARG, HOP_ERR_STATE = -1, -3
 HOP_FLAG_FEN, HOP_FLAG_HADME = 1, 2
 HOP_TU_RD_TS, HOP_TU_RD_KEEP = 1, 2
 HOP_DIST_SAD, HOP_DIST_SSE, HOP_DIST_HADS = 0, 1, 2
@@ -126,6 +127,25 @@ HOP_K_ENTROPY_CTX, HOP_K_ENTROPY = 21, 22          # hop_profile_read ids of hop
 HOP_K_PARSE = 23                                   # ... and of hop_slice_data_parse's launches
 HOP_K_ESCAPE, HOP_K_PICHASH = 24, 25               # ... of the emulation-prevention launches and the checksum pass (hop_access_unit_write, hop_rbsp_escape, hop_picture_hash)
 HOP_K_UNESCAPE = 26                                # ... of the count, scan and compact launches that remove emulation prevention (hop_rbsp_unescape, hop_access_unit_read / _decode)
+HOP_K_WALK_INTER, HOP_K_WALK_INTRA, HOP_K_WALK_INTRA_NXN = 12, 16, 20   # ... of the candidate walks (+ log2 CU size - 3 for the first two)
+
+# the stage stamps of the candidate walks (hop_walk_stamps_*: libhophip_stamps.so, loaded with HOP_LIB): stages, stamped kernels
+HOP_WS_COUNT = 15
+(HOP_WS_LEAF_FORWARD, HOP_WS_LEAF_ESTBITS, HOP_WS_LEAF_RDOQ, HOP_WS_LEAF_BITS, HOP_WS_LEAF_WAIT, HOP_WS_LEAF_INVERSE, HOP_WS_LEAF_DECIDE, HOP_WS_NODE_BEGIN, HOP_WS_NODE_SINGLE,
+ HOP_WS_NODE_CLOSE, HOP_WS_PREDICT, HOP_WS_COPY, HOP_WS_TAIL, HOP_WS_CU_BITS, HOP_WS_OTHER) = range(HOP_WS_COUNT)
+HOP_WSK_NAMES = ("k_inter_walk", "k_iw_begin", "k_iw_cand", "k_iw_pick", "k_iw_chroma", "k_iw_finish", "k_intra_walk")
+HOP_WSK_INTER_WALK, HOP_WSK_IW_BEGIN, HOP_WSK_IW_CAND, HOP_WSK_IW_PICK, HOP_WSK_IW_CHROMA, HOP_WSK_IW_FINISH, HOP_WSK_INTRA_WALK = range(7)
+HOP_WSK_COUNT = 7
+
+
+class WalkStampsTotal(ctypes.Structure):   # hop_walk_stamps_total
+    _fields_ = [("workgroups", ctypes.c_uint64), ("cycles", ctypes.c_uint64), ("realtime_ticks", ctypes.c_uint64), ("max_realtime_ticks", ctypes.c_uint64)]
+
+
+def walk_stamps_stage_names(L):
+    """hop_walk_stamps_stage_name for every stage, in the order of HOP_WS_*"""
+    L.hop_walk_stamps_stage_name.argtypes = [ctypes.c_int]; L.hop_walk_stamps_stage_name.restype = ctypes.c_char_p
+    return [L.hop_walk_stamps_stage_name(s).decode() for s in range(HOP_WS_COUNT)]
 
 
 PARSE_GUARD = 256   # bytes behind each output of the slice-data parser that must come back untouched
@@ -180,7 +200,7 @@ MIRRORS = {"hop_pu_job": PU_JOB_DTYPE, "hop_pu_result": PU_RESULT_DTYPE, "hop_pr
            "hop_rqt_result": RQT_RESULT_DTYPE, "hop_cu_syntax": CU_SYNTAX_DTYPE, "hop_intra_cu_syntax": INTRA_CU_SYNTAX_DTYPE, "hop_intra_rqt_opt": INTRA_RQT_OPT_DTYPE,
            "hop_intra_search_job": INTRA_SEARCH_JOB_DTYPE, "hop_intra_search_result": INTRA_SEARCH_RESULT_DTYPE, "hop_cu_part": CU_PART_DTYPE, "hop_enc_params": EncParams,
            "hop_deblock_params": DeblockParams, "hop_sao_param": SAO_PARAM_DTYPE, "hop_sao_params": SaoParams, "hop_dec_params": DecParams,
-           "hop_slice_data_params": SliceDataParams, "hop_stream_params": StreamParams, "hop_stream_info": StreamInfo}
+           "hop_slice_data_params": SliceDataParams, "hop_stream_params": StreamParams, "hop_stream_info": StreamInfo, "hop_walk_stamps_total": WalkStampsTotal}
 
 
 def mirror_size(m):
@@ -663,6 +683,28 @@ class Context:
         la, ms, un = ctypes.c_uint64(0), ctypes.c_double(0), ctypes.c_uint64(0)
         self._chk(self.L.hop_profile_read(self.h, read, ctypes.byref(la), ctypes.byref(ms), ctypes.byref(un)), "hop_profile_read")
         return int(la.value), float(ms.value), int(un.value)
+
+    def walk_stamps(self, kernel, log2_cu, nxn=0):
+        """hop_walk_stamps_read (the stamps library only; the product raises with code HOP_ERR_STATE): one row of the stage table since the last reset -> (cycles
+        (HOP_WS_COUNT,) uint64, visits (HOP_WS_COUNT,) uint64, {workgroups, cycles, realtime_ticks, max_realtime_ticks})"""
+        cyc = np.zeros(HOP_WS_COUNT, np.uint64); vis = np.zeros(HOP_WS_COUNT, np.uint64); tot = WalkStampsTotal()
+        self.L.hop_walk_stamps_read.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        self._chk(self.L.hop_walk_stamps_read(self.h, kernel, log2_cu, nxn, cyc.ctypes.data, vis.ctypes.data, ctypes.byref(tot)), "hop_walk_stamps_read")
+        return cyc, vis, {n: int(getattr(tot, n)) for n, _ in WalkStampsTotal._fields_}
+
+    def walk_stamps_reset(self):
+        """hop_walk_stamps_reset: the whole table to zero"""
+        self.L.hop_walk_stamps_reset.argtypes = [ctypes.c_void_p]
+        self._chk(self.L.hop_walk_stamps_reset(self.h), "hop_walk_stamps_reset")
+
+    def walk_stamps_probe(self):
+        """hop_walk_stamps_probe -> {stamp_cycles: two stamps back to back, mark_cycles: what a stage boundary charges when the next follows at once, clock_mhz: the
+        shader clock the stamps count, from the probe's span on both counters}"""
+        out = np.zeros(4, np.uint64)
+        self.L.hop_walk_stamps_probe.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        self._chk(self.L.hop_walk_stamps_probe(self.h, out.ctypes.data), "hop_walk_stamps_probe")
+        return {"stamp_cycles": int(out[0]), "mark_cycles": int(out[1]), "span_cycles": int(out[2]), "span_realtime_ticks": int(out[3]),
+                "clock_mhz": float(out[2]) / max(1.0, float(out[3])) * 100.0}
 
     def sao_reconstruct_params(self, coded, bit_depth=None):
         """hop_sao_reconstruct_params for this context's picture: coded (n_ctu, 3) SAO_PARAM_DTYPE -> what sao_apply takes"""

@@ -386,6 +386,7 @@ int hop_sizeof(const char* name) {
   S(hop_slice_data_params);
   S(hop_stream_params);
   S(hop_stream_info);
+  S(hop_walk_stamps_total);
 #undef S
   return -1;
 }

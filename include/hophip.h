@@ -1059,6 +1059,46 @@ int hop_profile_enable(hop_ctx* ctx, int on);
 int hop_profile_read(hop_ctx* ctx, int kernel, uint64_t* launches, double* total_ms, uint64_t* units);
 int hop_profile_reset(hop_ctx* ctx);
 
+/* ---- stage stamps of the candidate walks (csrc/k_walk.inl): a DIAGNOSTIC build, libhophip_stamps.so (csrc/k_cabac.hip compiled with -DHOP_WALK_STAMPS=1), whose walk
+ * kernels time their own stages.  Thread 0 of a workgroup -- the serial lane of every stage below -- reads the shader clock at each stage boundary and adds the cycles
+ * since the last boundary to the stage that was open; at the kernel's end the workgroup's sums go into a device table indexed by kernel, log2 CU size (3..6), NxN flag and
+ * stage.  The product library holds no stamp: there hop_walk_stamps_read / _reset / _probe return HOP_ERR_STATE (load the stamps library instead: HOP_LIB for hophip.py).
+ * The stamps fence the scheduler and drain the lane's memory counter, so the diagnostic build runs longer than the product: read SHARES of a timeline, not times. */
+enum {                        /* stages (one open at any time on thread 0's timeline) */
+  HOP_WS_LEAF_FORWARD = 0,    /* leaf: residual, forward transform / transform-skip scaling, scan, coefficients, states and entropy table into LDS, up to the barrier in front of the serial stages */
+  HOP_WS_LEAF_ESTBITS,        /* leaf, serial: the bit-estimate table (turd_setup_body) */
+  HOP_WS_LEAF_RDOQ,           /* leaf, serial: rdoq_tu */
+  HOP_WS_LEAF_BITS,           /* leaf, serial: the counted bits (cb_code_tu_at) */
+  HOP_WS_LEAF_WAIT,           /* leaf: the barrier behind the serial stages (wave leaves: thread 0 waits for the other waves' serial lanes) */
+  HOP_WS_LEAF_INVERSE,        /* leaf: store of the levels, dequantiser, inverse transform, reconstruction, distortion */
+  HOP_WS_LEAF_DECIDE,         /* leaf, serial: the cbf-zero decision (turd_decide_body) */
+  HOP_WS_NODE_BEGIN,          /* rqt_begin_body, irqt_begin_body, ic_begin_body, is_prep_body */
+  HOP_WS_NODE_SINGLE,         /* rqt_single_body, irqt_single_body, ic_single_body */
+  HOP_WS_NODE_CLOSE,          /* rqt_close_body, irqt_close_body, ic_fold_body */
+  HOP_WS_PREDICT,             /* intra_rough_body, intra_pred_body, intra_pred_chroma_body */
+  HOP_WS_COPY,                /* irqt_copy_body, ic_park_body, is_keep_body, ic_keep_body, the bands' preparation, a winner's arrays kept */
+  HOP_WS_TAIL,                /* rqt_final_body, fin_*, the reconstruction of the final jobs, irqt_final_body, is_pick_body, the commit bodies */
+  HOP_WS_CU_BITS,             /* cu_bits_body, intra_cu_total_body, ic_bits_body */
+  HOP_WS_OTHER,               /* what lies between two named stages: table fill, init bodies, the candidate list, loop control */
+  HOP_WS_COUNT
+};
+enum { HOP_WSK_INTER_WALK = 0, HOP_WSK_IW_BEGIN, HOP_WSK_IW_CAND, HOP_WSK_IW_PICK, HOP_WSK_IW_CHROMA, HOP_WSK_IW_FINISH, HOP_WSK_INTRA_WALK, HOP_WSK_COUNT };   /* the stamped kernels */
+typedef struct {
+  uint64_t workgroups;           /* workgroups that ran to their end */
+  uint64_t cycles;               /* sum over workgroups of (last stamp - first stamp), from the two stamps themselves (the stages must add up to it) */
+  uint64_t realtime_ticks;       /* the same span on the constant 100 MHz counter, summed ... */
+  uint64_t max_realtime_ticks;   /* ... and the longest single workgroup */
+} hop_walk_stamps_total;
+/* waits for the context's streams, then copies one row of the table: cycles and visits per stage since the last reset (each may be NULL) */
+int hop_walk_stamps_read(hop_ctx* ctx, int kernel /* HOP_WSK_* */, int log2_cu /* 3..6 */, int nxn /* 0 / 1 */, uint64_t cycles[HOP_WS_COUNT], uint64_t visits[HOP_WS_COUNT],
+                         hop_walk_stamps_total* total);
+int hop_walk_stamps_reset(hop_ctx* ctx);
+/* what the instrument costs and which clock it reads, from a one-workgroup probe kernel: out[0] the smallest difference of two stamps back to back (cycles), out[1] the
+ * mean cycles a stage boundary charges to the stage it opens when the next boundary follows at once (stamp + bookkeeping), out[2] / out[3] one span of the probe in shader
+ * cycles / in 100 MHz ticks: the in-kernel clock is out[2] / out[3] x 100 MHz */
+int hop_walk_stamps_probe(hop_ctx* ctx, uint64_t out[4]);
+const char* hop_walk_stamps_stage_name(int stage);   /* "LEAF_FORWARD" ...; NULL outside 0 .. HOP_WS_COUNT - 1 (both libraries) */
+
 /* library/build identification: "hophip <version> gfx950" */
 const char* hop_version(void);
 
