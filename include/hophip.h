@@ -301,6 +301,13 @@ int hop_rdoq(hop_ctx* ctx, int n, const hop_rdoq_job* jobs, int n_tables, const 
              const int32_t* src, int32_t* dst, uint32_t* abs_sum);
 int hop_rdoq_device(hop_ctx* ctx, int n, const hop_rdoq_job* d_jobs, const hop_estbits* d_tables, const int32_t* d_src,
                     int32_t* d_dst, uint32_t* d_abs_sum);                                           /* asynchronous, unchecked */
+/* host only: the device bodies of one TU compiled for the host (host/hop_rdoq_host.cpp from csrc/k_rdoq_dev.inl) -- yardsticks that the CPU tests drive, not a CPU path of
+ * the library.  src / dst are the TU's own N x N coefficients and levels (coeff_offset and estbits_index are not read); the work area and every other intermediate array
+ * are filled with the byte `fill` (0..255) first: the outputs must not depend on it.
+ * hop_rdoq_tu_host: the one-lane body of hop_rdoq's kernels.  hop_rdoq_tu_phased_host: the phased form of the fused leaf step -- preparation and finish spread over `nlanes`
+ * (1..1024) emulated lanes, the recurrence on one --, the lanes of each phase run in ascending (descending = 0) or descending order.  Same bytes in dst and abs_sum. */
+int hop_rdoq_tu_host(const hop_rdoq_job* job, const hop_estbits* table, const int32_t* src, int32_t* dst, uint32_t* abs_sum, int fill);
+int hop_rdoq_tu_phased_host(const hop_rdoq_job* job, const hop_estbits* table, const int32_t* src, int32_t* dst, uint32_t* abs_sum, int fill, int nlanes, int descending);
 
 /* ---- CABAC bit estimator for residual coding (building block of rows a0 / a8 / a8b; feeds a11) ---- */
 /* Context states (ContextModel::m_ucState = state << 1 | MPS) of the sets residual coding uses, in the reference's set
@@ -378,6 +385,11 @@ int hop_tu_rd(hop_ctx* ctx, int n, const hop_tu_rd_job* jobs, int n_ctx, const h
 /* d_coef_offsets[i] = first level of TU i in d_levels (n_coeff entries in total) */
 int hop_tu_rd_device(hop_ctx* ctx, int n, const hop_tu_rd_job* d_jobs, const hop_cabac_ctx* d_ctx_in, const int64_t* d_coef_offsets, size_t n_coeff,
                      int32_t* d_levels, hop_tu_rd_result* d_results);                                 /* asynchronous, unchecked */
+/* host only, yardsticks like hop_rdoq_tu_host (csrc/k_estbits_dev.inl compiled for the host): the bit-estimate table the leaf step derives for `job` (log2_size and comp
+ * are read) from the context states `ctx`, as one lane writes it (hop_estbits_setup_host: the table is cleared, then filled) and as `nlanes` (1..1024) lanes fill it side
+ * by side, in ascending or descending lane order (hop_estbits_fill_host: every one of the table's 976 bytes is written, nothing is cleared first).  Same bytes. */
+int hop_estbits_setup_host(const hop_tu_rd_job* job, const hop_cabac_ctx* ctx, hop_estbits* out);
+int hop_estbits_fill_host(const hop_tu_rd_job* job, const hop_cabac_ctx* ctx, hop_estbits* out, int nlanes, int descending);
 
 /* ---- the mode-decision half of the intra rough search (rest of row a7) ---- */
 /* replaces: the candidate selection of TEncSearch::estIntraPredQT (TLibEncoder/TEncSearch.cpp:2440-2493) on the 35 SATDs of hop_intra_rough: per mode
