@@ -11,7 +11,6 @@
 // index handed to the micro-image candidates.
 #include "hop_spine.h"
 #include <map>
-#include <deque>
 #include <exception>
 #include <math.h>
 #include <stdlib.h>
@@ -30,8 +29,6 @@
 #endif
 
 namespace hopspine {
-
-bool posted_requests_allowed = true;
 
 void Backend::wait_counter(std::atomic<int>* ctr, int target) { while (ctr->load() < target) std::this_thread::yield(); }
 
@@ -232,7 +229,6 @@ class CtuWorker {
   void wait_above(int col);
   bool abandoned_ = false;                                                // a candidate child of this worker gave its CTU up (Abandoned): the worker follows once its children have ended
   void fork_cands(int n, const std::function<void(int)>& fn);
-  bool raster_below_ = [] { const char* e = getenv("HOP_SPINE_RASTER_BELOW"); return e ? atoi(e) != 0 : true; }();
   struct PendingSave { bool on; int d, x, y, size; } psave_ = { false, 0, 0, 0, 0 };
   void flush_save();
   void check_merge_2Nx2N(int d, bool* early_skip);
@@ -298,8 +294,8 @@ bool CtuWorker::valid_pattern(int px, int py, int w, int h, int mvx, int mvy) {
     int x = (int)bx - 80, y = (int)by - 80;
     x = x < 0 ? 0 : x >= cfg.pic_w ? cfg.pic_w - 1 : x; y = y < 0 ? 0 : y >= cfg.pic_h ? cfg.pic_h - 1 : y;
     if (y < ctu_y_) wait_above(x >> 6);                              // exact wavefront: the reference has the rows above whole
-    if ((raster_below_ || cfg.exact) && y >= ctu_y_ + CTU) return false;            // the reference codes in raster order: nothing below the current CTU row exists yet, whatever a CTU row that
-                                                                      // runs behind this one in the wavefront has committed there (HOP_SPINE_RASTER_BELOW=0: as the map has it)
+    if (y >= ctu_y_ + CTU) return false;                             // the reference codes in raster order: nothing below the current CTU row exists yet, whatever a CTU row that
+                                                                      // runs behind this one in the wavefront has committed there
     return E.committed[(size_t)(y >> 3) * W8 + (x >> 3)] != 0;
   };
   const long lb = (long)(py + (mvy >> 2) + h + 4) * stride + (px + (mvx >> 2));
@@ -1232,14 +1228,13 @@ void Encoder::encode_frame(int first_ctus) {
 // batches (FiberPool), or one thread per row on backends of their own
 // ---------------------------------------------------------------------------------------------------------------------------------
 namespace {
-struct Req { int kind; int n; const void* a; const void* b; void* out; int i0, i1, i2, i3; bool done; uint64_t tag; bool posted; int worker; };
-enum { RQ_ME, RQ_PRED, RQ_DIST, RQ_VALID, RQ_INTER, RQ_INTRA, RQ_SAVE, RQ_RESTORE, RQ_COMMIT, RQ_PCOST, RQ_NOP };   // RQ_NOP: nothing but the round (FiberPool::flush)
-static Req req(int kind, int n, const void* a, const void* b, void* out, int i0 = 0, int i1 = 0, int i2 = 0, int i3 = 0) { Req q = { kind, n, a, b, out, i0, i1, i2, i3, false, 0, false, 0 }; return q; }
+struct Req { int kind; int n; const void* a; const void* b; void* out; int i0, i1, i2, i3; bool done; uint64_t tag; };
+enum { RQ_ME, RQ_PRED, RQ_DIST, RQ_VALID, RQ_INTER, RQ_INTRA, RQ_SAVE, RQ_RESTORE, RQ_COMMIT, RQ_PCOST };
+static Req req(int kind, int n, const void* a, const void* b, void* out, int i0 = 0, int i1 = 0, int i2 = 0, int i3 = 0) { Req q = { kind, n, a, b, out, i0, i1, i2, i3, false, 0 }; return q; }
 
 // one group of requests of the same kind (and class) as one call of the batching backend
 static void run_group(BatchInner* inner_, std::vector<Req*>& g) {
   const int kind = g[0]->kind;
-  if (kind == RQ_NOP) return;
   if (kind == RQ_ME) {
     std::vector<hop_pu_job> j; for (Req* r : g) j.insert(j.end(), (const hop_pu_job*)r->a, (const hop_pu_job*)r->a + r->n);
     std::vector<hop_pu_result> o(j.size());
@@ -1301,7 +1296,7 @@ class FiberPool : public Backend {
                  Fiber* parent; int live_children; bool wait_children; uint64_t tag;      // parent: a child of fork_join (recycled when done)
                  std::atomic<int>* wait_ctr; int wait_target; };                        // waiting until *wait_ctr >= wait_target
   FiberPool(BatchInner* inner, int n_workers) : rounds(0), requests(0), inner_(inner), T_(n_workers), failed_(false), finished_(false), arrived_(0), gen_(0), left_(0), idle_rounds_(0) {
-    sched_.resize(T_); mine_.resize(T_); local_.resize(T_); free_.resize(T_); kids_.resize(T_); pstore_.resize(T_); pjobs_.resize(T_);
+    sched_.resize(T_); mine_.resize(T_); local_.resize(T_); free_.resize(T_); kids_.resize(T_);
   }
   ~FiberPool() { for (Fiber* f : all_) { stack_free(f->stack); delete f; } for (auto& v : kids_) for (Fiber* f : v) { stack_free(f->stack); delete f; } }
   void add(std::function<void()> body) {
@@ -1340,21 +1335,16 @@ class FiberPool : public Backend {
   void set_tag(int, uint64_t tag) { current()->tag = tag; }            // the tag belongs to the fiber (children of fork_join carry their own)
   void begin_frame() {}
   void me_search(int, int n, const hop_pu_job* j, hop_pu_result* r) { Req q = req(RQ_ME, n, j, NULL, r); submit(q); }
-  void pred_inter(int, int n, const hop_pred_job* j) { Req q = req(RQ_PRED, n, j, NULL, NULL); if (posted_preds_) post(q, j); else submit(q); }
+  void pred_inter(int, int n, const hop_pred_job* j) { Req q = req(RQ_PRED, n, j, NULL, NULL); submit(q); }
   void distortion(int, int n, const hop_dist_job* j, uint32_t* o) { Req q = req(RQ_DIST, n, j, NULL, o); submit(q); }
   void valid_pattern(int, int n, const int32_t* v, uint8_t* o) { Req q = req(RQ_VALID, n, v, NULL, o); submit(q); }
   void pred_cost(int, int n, const hop_pred_job* j, int kind, uint32_t* o) { Req q = req(RQ_PCOST, n, j, NULL, o, kind); submit(q); }
   void inter_cu(int, const InterEval& e, const Coder& in, EvalResult& o) { Req q = req(RQ_INTER, 1, &e, &in, &o, e.job.log2_cu, e.skip_res); submit(q); }
   void intra_cu(int, const IntraEval& e, const Coder& in, EvalResult& o) { Req q = req(RQ_INTRA, 1, &e, &in, &o, e.job.log2_cu, e.part_nxn); submit(q); }
-  void recon_save(int lane, int slot, int x, int y, int size) { Req q = req(RQ_SAVE, 1, NULL, NULL, NULL, x, y, size, lane * 16 + slot); if (posted_mode_ && (posted_kinds_ & 1)) post(q, NULL); else submit(q); }
-  void recon_restore(int lane, int slot, int x, int y, int size) { Req q = req(RQ_RESTORE, 1, NULL, NULL, NULL, x, y, size, lane * 16 + slot); if (posted_mode_ && (posted_kinds_ & 2)) post(q, NULL); else submit(q); }
-  void commit(int, int x, int y, int size) { Req q = req(RQ_COMMIT, 1, NULL, NULL, NULL, x, y, size); if (posted_mode_ && (posted_kinds_ & 4)) post(q, NULL); else submit(q); }
-  // everything this fiber has posted is on the device when this returns (a CTU is only counted as retired, and handed to other ranks, behind it)
-  void flush() { if (!posted_mode_) return; Req q = req(RQ_NOP, 1, NULL, NULL, NULL); submit(q); }
-  void restore_commit(int lane, int slot, int x, int y, int size) {
-    if (posted_mode_) { recon_restore(lane, slot, x, y, size); commit(lane, x, y, size); return; }
-    Req q = req(RQ_COMMIT, 1, NULL, NULL, NULL, x, y, size, lane * 16 + slot + 1); submit(q);
-  }
+  void recon_save(int lane, int slot, int x, int y, int size) { Req q = req(RQ_SAVE, 1, NULL, NULL, NULL, x, y, size, lane * 16 + slot); submit(q); }
+  void recon_restore(int lane, int slot, int x, int y, int size) { Req q = req(RQ_RESTORE, 1, NULL, NULL, NULL, x, y, size, lane * 16 + slot); submit(q); }
+  void commit(int, int x, int y, int size) { Req q = req(RQ_COMMIT, 1, NULL, NULL, NULL, x, y, size); submit(q); }
+  void restore_commit(int lane, int slot, int x, int y, int size) { Req q = req(RQ_COMMIT, 1, NULL, NULL, NULL, x, y, size, lane * 16 + slot + 1); submit(q); }
   void wait_counter(std::atomic<int>* ctr, int target) {                // until *ctr >= target (another fiber counts it up)
     if (ctr->load() >= target) return;
     Fiber* f = current(); f->wait_ctr = ctr; f->wait_target = target;
@@ -1391,19 +1381,6 @@ class FiberPool : public Backend {
     sp[6] = (void*)&tramp; sp[7] = NULL;
     f->sp = sp;
   }
-  // A request without an answer (a prediction into the resident picture, a reconstruction put aside or brought back, a commit to the SS reference) need not stop its
-  // row: it is handed over and the row goes on; the next time requests are served, everything posted is issued first -- the stash / commit requests in the order each
-  // worker received them, then the predictions -- and only then the requests rows are waiting for.  A row's own order is kept (whatever consumes a posted request's effect
-  // is a waiting request of the same row, or a row of a later wavefront step, whose first request waits), and rounds that served nothing but such requests disappear
-  // (HOP_SPINE_POSTED=1; off by default until measured on the device: tests/test_spine_cpu.py runs both ways).
-  void post(Req& q, const hop_pred_job* jobs) {
-    if (failed_) throw 1;
-    Fiber* f = current(); const int w = f->worker;
-    q.tag = f->tag; q.posted = true; q.worker = w;
-    if (jobs) { pjobs_[w].emplace_back(jobs, jobs + q.n); q.a = pjobs_[w].back().data(); }
-    pstore_[w].push_back(q);
-    local_[w].push_back(&pstore_[w].back());
-  }
   void submit(Req& q) {
     if (failed_) throw 1;
     Fiber* f = current();
@@ -1438,14 +1415,14 @@ class FiberPool : public Backend {
       if (!barrier(w)) break;
     }
   }
-  int spin_us_ = [] { const char* e = getenv("HOP_SPINE_SPIN_US"); return e ? atoi(e) : 200; }();   // how long a waiting worker watches the generation before it sleeps
+  enum { SPIN_US = 200 };                                               // how long a waiting worker watches the generation before it sleeps (measured: no effect, below)
   bool barrier(int) {                                                   // false: everything has finished
     std::unique_lock<std::mutex> lk(bm_);
     const uint64_t gen = gen_.load();
     if (++arrived_ == T_) {                                             // every worker is out of runnable rows: serve, or finish
       lk.unlock();                                                      // (the others only watch gen_ from here on)
       for (int k = 0; k < T_; k++) { pending_.insert(pending_.end(), local_[k].begin(), local_[k].end()); local_[k].clear(); }
-      if (left_.load() == 0) { if (posted_mode_ && !pending_.empty() && !failed_) { try { serve_posted(); } catch (...) { failed_ = true; } } finished_ = true; }
+      if (left_.load() == 0) finished_ = true;
       else if (failed_) pending_.clear();
       else if (!pending_.empty() || !inflight_.empty()) { serve(); idle_rounds_ = 0; }
       else if (++idle_rounds_ > 100000) failed_ = true;                 // rows waiting for a step nobody can finish
@@ -1460,7 +1437,7 @@ class FiberPool : public Backend {
     const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
     for (unsigned spin = 0; gen_.load(std::memory_order_acquire) == gen; spin++) {
       __builtin_ia32_pause();
-      if ((spin & 255) == 255 && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(spin_us_)) {
+      if ((spin & 255) == 255 && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(SPIN_US)) {
         lk.lock();
         bcv_.wait(lk, [&] { return gen_.load() != gen; });
         lk.unlock();
@@ -1469,29 +1446,23 @@ class FiberPool : public Backend {
     }
     return !finished_;
   }
-  void serve_posted() {                                                 // everything posted since the last serve, out of pending_
-    std::vector<std::vector<Req*> > seq(T_); std::vector<Req*> preds, rest;
-    for (Req* r : pending_) { if (!r->posted) rest.push_back(r); else if (r->kind == RQ_PRED) preds.push_back(r); else seq[r->worker].push_back(r); }
-    if (rest.size() == pending_.size()) return;
-    std::vector<size_t> at(T_, 0);
-    for (;;) {                                                            // stash / commit requests: waves of one kind, every worker's next run of that kind
-      int kind = -1; for (int w = 0; w < T_ && kind < 0; w++) if (at[w] < seq[w].size()) kind = seq[w][at[w]]->kind;
-      if (kind < 0) break;
+  // v as one run_group per kind, the evaluations per class (i0, i1) too: the groups in the order of their first request, every group in the order of v
+  void run_groups(const std::vector<Req*>& v) {
+    std::vector<char> used(v.size(), 0);
+    for (size_t i = 0; i < v.size(); i++) {
+      if (used[i]) continue;
       std::vector<Req*> g;
-      for (int w = 0; w < T_; w++) while (at[w] < seq[w].size() && seq[w][at[w]]->kind == kind) g.push_back(seq[w][at[w]++]);
-      run_group(inner_, g); requests += g.size();
+      for (size_t k = i; k < v.size(); k++) {
+        if (used[k] || v[k]->kind != v[i]->kind) continue;
+        if ((v[i]->kind == RQ_INTER || v[i]->kind == RQ_INTRA) && (v[k]->i0 != v[i]->i0 || v[k]->i1 != v[i]->i1)) continue;
+        used[k] = 1; g.push_back(v[k]);
+      }
+      run_group(inner_, g);
     }
-    if (!preds.empty()) { run_group(inner_, preds); requests += preds.size(); }
-    pending_.swap(rest);
-    for (int w = 0; w < T_; w++) { pstore_[w].clear(); pjobs_[w].clear(); }
   }
   void serve() {
     struct Clock { double& acc; std::chrono::steady_clock::time_point t0; explicit Clock(double& a) : acc(a), t0(std::chrono::steady_clock::now()) {}
                    ~Clock() { acc += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); } } clock(serve_s);
-    if (posted_mode_) {
-      try { serve_posted(); } catch (...) { failed_ = true; }
-      if (failed_ || (pending_.empty() && inflight_.empty())) return;
-    }
     // the requests with the smallest tag; with candidates side by side (tag_shift = 20) the tag is cut down to the quadtree node: the candidates of a node are at
     // different steps of their chains at any moment, and all of them are served -- one launch chain per kind and class present
     uint64_t tmin = ~0ull; for (Req* r : pending_) if ((r->tag >> tag_shift) < tmin) tmin = r->tag >> tag_shift;
@@ -1514,41 +1485,23 @@ class FiberPool : public Backend {
         v.swap(keep);
       }
       // ... and among the short chains the motion searches (a dozen dependent launches, ten times a prediction request) once nothing cheaper of the node is waiting: the
-      // candidates and CTUs that are a few cheap requests behind catch up first, and their searches then share the chain instead of taking one each
-      if (defer_me_) {
-        bool cheap = false; for (Req* r : v) cheap |= (r->kind != RQ_ME && r->kind != RQ_INTER && r->kind != RQ_INTRA);
-        if (cheap) {
-          std::vector<Req*> keep;
-          for (Req* r : v) (r->kind == RQ_ME ? rest : keep).push_back(r);
-          v.swap(keep);
-        }
+      // candidates and CTUs that are a few cheap requests behind catch up first, and their searches then share the chain instead of taking one each (34 -> 49 CTU/s)
+      bool cheap = false; for (Req* r : v) cheap |= (r->kind != RQ_ME && r->kind != RQ_INTER && r->kind != RQ_INTRA);
+      if (cheap) {
+        std::vector<Req*> keep;
+        for (Req* r : v) (r->kind == RQ_ME ? rest : keep).push_back(r);
+        v.swap(keep);
       }
     }
     pending_.swap(rest);
     rounds++; requests += v.size() + early.size();
     try {
-      if (!early.empty()) {                                               // one group per class, issued and left in flight
-        std::vector<char> used(early.size(), 0);
-        for (size_t i = 0; i < early.size(); i++) {
-          if (used[i]) continue;
-          std::vector<Req*> g;
-          for (size_t k = i; k < early.size(); k++) if (!used[k] && early[k]->i0 == early[i]->i0 && early[k]->i1 == early[i]->i1) { used[k] = 1; g.push_back(early[k]); }
-          run_group(inner_, g);
-        }
+      if (!early.empty()) {                                               // (all intra evaluations: one group per class) issued and left in flight
+        run_groups(early);
         inflight_.insert(inflight_.end(), early.begin(), early.end());
       }
       { unsigned mask = 0; for (Req* r : v) mask |= 1u << r->kind; round_masks_[mask]++; }
-      std::vector<char> used(v.size(), 0);
-      for (size_t i = 0; i < v.size(); i++) {
-        if (used[i]) continue;
-        std::vector<Req*> g;
-        for (size_t k = i; k < v.size(); k++) {
-          if (used[k] || v[k]->kind != v[i]->kind) continue;
-          if ((v[i]->kind == RQ_INTER || v[i]->kind == RQ_INTRA) && (v[k]->i0 != v[i]->i0 || v[k]->i1 != v[i]->i1)) continue;
-          used[k] = 1; g.push_back(v[k]);
-        }
-        run_group(inner_, g);
-      }
+      run_groups(v);
       // a round without evaluations leaves what was issued ahead in flight; one with evaluations (or one that has nothing else to wait for) collects everything
       bool heavy = v.empty(); for (Req* r : v) heavy |= (r->kind == RQ_INTER || r->kind == RQ_INTRA);
       for (Req* r : inflight_) heavy |= (r->tag >> tag_shift) < tmin;     // nothing else of that node is waiting any more
@@ -1564,18 +1517,6 @@ class FiberPool : public Backend {
  public:
   void print_round_stats() { if (!getenv("HOP_SPINE_ROUND_STATS")) return; for (auto& kv : round_masks_) fprintf(stderr, "hop spine rounds: kinds %03x x %llu\n", kv.first, (unsigned long long)kv.second); }
  private:
-  bool defer_me_ = [] { const char* e = getenv("HOP_SPINE_DEFER_ME"); return e ? atoi(e) != 0 : true; }();
-  // HOP_SPINE_POSTED: 0 (default) -- every request waits for its round; 1 -- the requests that have no answer and touch nothing another pending request reads (a reconstruction put aside or brought back, an
-  // SS-reference commit) do not stop their row: they are handed over and issued first at the next serve, every worker's in its order; 2 -- predictions without a cost too
-  // (only where they still are requests of their own, HOP_SPINE_FUSE_PRED=0; on the device a batch of posted predictions is one launch and two predictions of one block would
-  // lose their order, so the device backend never allows 2: posted_requests_allowed).  Level 1 with restore + commit measured on the device at one picture's breadth: 14 %
-  // fewer rounds, no gain (77.5 against 78.8 - 79.3 CTU/s): off
-  int posted_level_ = [] { const char* e = getenv("HOP_SPINE_POSTED"); int v = e ? atoi(e) : 0; if (v > 1 && !posted_requests_allowed) v = 1; return v < 0 ? 0 : v; }();
-  bool posted_mode_ = posted_level_ >= 1, posted_preds_ = posted_level_ >= 2;
-  // which of them are posted at level 1: 1 stash, 2 restore, 4 commit.  Restore and commit by default; a posted stash failed on the device -- one picture of the GPU tests
-  // (448x192, --MIsize=15, 16 slots: an intra candidate rated from a stale neighbourhood), cause not found, the CPU spine is fine with it -- and stays a request of its own
-  int posted_kinds_ = [this] { const char* e = getenv("HOP_SPINE_POSTED_KINDS"); return e ? atoi(e) : (posted_level_ >= 2 ? 7 : 6); }();
-  std::vector<std::deque<Req> > pstore_; std::vector<std::deque<std::vector<hop_pred_job> > > pjobs_;   // per worker: what was posted since the last serve (deques: addresses stay)
   std::vector<Req*> inflight_;
   BatchInner* inner_; int T_; volatile bool failed_; bool finished_;
   std::vector<void*> sched_; std::vector<std::vector<Fiber*> > mine_; std::vector<std::vector<Req*> > local_; std::vector<Fiber*> all_; std::vector<Req*> pending_;
@@ -1622,8 +1563,8 @@ struct WavefrontSteps {
   std::mutex m_; std::condition_variable cv_; std::vector<Coder> sync_;
 };
 
-// Row r of picture p, CTU by CTU as its steps come up, through `be`.  wait_step(s) returns once every step <= s is finished (and throws when the wavefront has failed);
-// flush, if any, runs after every CTU before it counts.  Honours hop_encode_cancel, counts hop_encode_progress; whatever ends the row early, the rows below are released.
+// Row r of picture p, CTU by CTU as its steps come up, through `be`.  wait_step(s) returns once every step <= s is finished (and throws when the wavefront has failed).
+// Honours hop_encode_cancel, counts hop_encode_progress; whatever ends the row early, the rows below are released.
 //
 // Exact wavefront (EncConfig::exact): no steps.  A CTU that waits for a column of the row above `lag` or more ahead would wait for a later step, which cannot start before
 // the waiting CTU ends; so the rows are gated on each other's progress instead: row r starts CTU c once row r - 1 has retired CTU min(c + lag - 1, cols - 1)
@@ -1637,7 +1578,7 @@ struct WavefrontSteps {
 // k (lag - 1) + 1 + c retired CTUs are certain, not k lag + c -- and a row could meet the row rif above it on its lane.  So row r first waits until row r - rif has ENDED
 // (row_gate = ROW_ENDED, stored after that row's last use of the lane).  That is again a wait for a row above, which ends by the induction above, so the no-deadlock
 // argument stands; Encoder::lane_rows counts the rows on a lane and a second one is an error, not a silent overwrite.  A failure anywhere ends every row at its next gate.
-static void code_row(Encoder& E, int p, int r, int lane, Backend* be, WavefrontSteps& ws, const Coder& init, const std::function<void(int)>& wait_step, const std::function<void()>& flush, uint64_t& n_cand) {
+static void code_row(Encoder& E, int p, int r, int lane, Backend* be, WavefrontSteps& ws, const Coder& init, const std::function<void(int)>& wait_step, uint64_t& n_cand) {
   const EncConfig& cfg = E.config();
   CtuWorker* w = NULL;
   std::exception_ptr err;
@@ -1671,7 +1612,6 @@ static void code_row(Encoder& E, int p, int r, int lane, Backend* be, WavefrontS
       try { w->compress_ctu(a, k, next); }
       catch (const Abandoned&) { E.ctu_trace[a].clear(); break; }       // (exact wavefront) given up: not retired, its results stay 0
       k = next;
-      if (flush) flush();                                               // (posted stash / restore / commit requests of the CTU: done before it counts)
       if (cfg.progress) cfg.progress->fetch_add(1);
       if (c == 1) ws.store_sync(p, r, k);
       if (ws.world > 1) E.ctu_exit[a] = k;                              // (travels to the other ranks)
@@ -1686,6 +1626,53 @@ static void code_row(Encoder& E, int p, int r, int lane, Backend* be, WavefrontS
   if (exact) E.row_gate[r].store(Encoder::ROW_ENDED);
   ws.abandon(r, c);
   if (err) std::rethrow_exception(err);
+}
+
+// One picture's rows dealt to several ranks: the body of the exchange fiber.  Step after step, once this rank's CTUs of the step are finished -- their records out,
+// everybody's in (an all-gather of equally sized slot tables: slot 0 of a rank carries its cancel request), the other ranks' CTUs written into the picture on this side,
+// then the next step may start
+struct ShardRec { int32_t addr, valid; double cost; uint32_t bits, dist; uint32_t frac, pad; Coder entry, exit; Part parts[256]; int16_t y[4096], cb[1024], cr[1024]; };
+static void exchange_steps(Encoder& E, BatchInner* inner, FiberPool& pool, WavefrontSteps& ws) {
+  const EncConfig& cfg = E.config();
+  const int rows = ws.rows, cols = ws.cols, lag = ws.lag, world = ws.world, rank = ws.rank;
+  auto count_of = [&](int g, int s) { int n = 0; for (int r = g; r < rows; r += world) { const int c = s - lag * r; n += (c >= 0 && c < cols); } return n; };
+  std::vector<ShardRec> sendb, recvb;
+  for (int s = 0; s < ws.n_steps; s++) {
+    pool.wait_counter(&ws.finished[s], ws.in_step[s]);
+    int slots = 0; for (int g = 0; g < world; g++) slots = std::max(slots, count_of(g, s));
+    sendb.assign((size_t)slots + 1, ShardRec()); recvb.resize((size_t)world * (slots + 1));
+    memset(&sendb[0], 0, sizeof(ShardRec) * sendb.size());
+    sendb[0].addr = -1; sendb[0].valid = (cfg.cancel && cfg.cancel->load()) ? 1 : 0;
+    int q = 1;
+    for (int r = rank; r < rows; r += world) {
+      const int c = s - lag * r; if (c < 0 || c >= cols) continue;
+      const int a = r * cols + c, x = c * CTU, y = r * CTU, w = std::min(CTU, cfg.pic_w - x), h = std::min(CTU, cfg.pic_h - y);
+      ShardRec& t = sendb[q++];
+      t.addr = a; t.valid = 1; t.cost = E.ctu_cost[a]; t.bits = E.ctu_bits[a]; t.dist = E.ctu_dist[a]; t.frac = E.ctu_rd_fraction[a]; t.entry = E.ctu_entry[a]; t.exit = E.ctu_exit[a];
+      memcpy(t.parts, &E.pic[(size_t)a * 256], sizeof(t.parts));
+      inner->export_block(x, y + cfg.y_origin, w, h, t.y, t.cb, t.cr);
+    }
+    cfg.shard->allgather(&sendb[0], &recvb[0], sizeof(ShardRec) * sendb.size());
+    bool any_cancel = false;
+    for (int g = 0; g < world; g++) {
+      const ShardRec* rr = &recvb[(size_t)g * (slots + 1)];
+      any_cancel |= rr[0].valid != 0;
+      if (g == rank) continue;
+      for (int k2 = 1; k2 <= slots; k2++) {
+        const ShardRec& t = rr[k2];
+        if (!t.valid) continue;
+        const int a = t.addr, c = a % cols, r = a / cols, x = c * CTU, y = r * CTU, w = std::min(CTU, cfg.pic_w - x), h = std::min(CTU, cfg.pic_h - y);
+        if (a < 0 || a >= E.n_ctu() || r % world != g) throw 1;
+        E.ctu_cost[a] = t.cost; E.ctu_bits[a] = t.bits; E.ctu_dist[a] = t.dist; E.ctu_rd_fraction[a] = (uint16_t)t.frac; E.ctu_entry[a] = t.entry; E.ctu_exit[a] = t.exit;
+        memcpy(&E.pic[(size_t)a * 256], t.parts, sizeof(t.parts));
+        for (int yy = y >> 3; yy < (y + h) >> 3; yy++) memset(&E.committed[(size_t)yy * (cfg.pic_w >> 3) + (x >> 3)], 1, w >> 3);
+        if (c == 1) ws.store_sync(0, r, t.exit);
+        inner->import_block(x, y + cfg.y_origin, w, h, t.y, t.cb, t.cr);
+      }
+    }
+    if (any_cancel) { ws.agreed_cancel.store(1); ws.steps_complete.store(ws.n_steps - 1); break; }   // every rank has seen it at this step: the rows stop at their next CTU
+    ws.steps_complete.store(s);
+  }
 }
 }  // namespace
 
@@ -1740,54 +1727,10 @@ void Encoder::wavefront_many(Encoder* const* encs, int n_pic, BatchInner* inner,
     for (int p = 0; p < n_pic; p++) for (int r = 0; r < rows; r++) {
       if (!ws.owned(r)) continue;
       pool.add([&, p, r]() {
-        code_row(*encs[p], p, r, lane_of(p, r), &pool, ws, init, [&](int st) { pool.wait_counter(&ws.steps_complete, st); }, [&]() { pool.flush(); }, cand[(size_t)p * rows + r]);
+        code_row(*encs[p], p, r, lane_of(p, r), &pool, ws, init, [&](int st) { pool.wait_counter(&ws.steps_complete, st); }, cand[(size_t)p * rows + r]);
       });
     }
-    // the exchange fiber: step after step, once this rank's CTUs of the step are finished -- their records out, everybody's in (an all-gather of equally sized slot tables:
-    // slot 0 of a rank carries its cancel request), the other ranks' CTUs written into the picture on this side, then the next step may start
-    struct ShardRec { int32_t addr, valid; double cost; uint32_t bits, dist; uint32_t frac, pad; Coder entry, exit; Part parts[256]; int16_t y[4096], cb[1024], cr[1024]; };
-    if (world > 1) pool.add([&]() {
-      Encoder& E = E0;
-      const EncConfig& cfg = E.cfg_;
-      auto count_of = [&](int g, int s) { int n = 0; for (int r = g; r < rows; r += world) { const int c = s - lag * r; n += (c >= 0 && c < cols); } return n; };
-      std::vector<ShardRec> sendb, recvb;
-      for (int s = 0; s < ws.n_steps; s++) {
-        pool.wait_counter(&ws.finished[s], ws.in_step[s]);
-        int slots = 0; for (int g = 0; g < world; g++) slots = std::max(slots, count_of(g, s));
-        sendb.assign((size_t)slots + 1, ShardRec()); recvb.resize((size_t)world * (slots + 1));
-        memset(&sendb[0], 0, sizeof(ShardRec) * sendb.size());
-        sendb[0].addr = -1; sendb[0].valid = (cfg.cancel && cfg.cancel->load()) ? 1 : 0;
-        int q = 1;
-        for (int r = rank; r < rows; r += world) {
-          const int c = s - lag * r; if (c < 0 || c >= cols) continue;
-          const int a = r * cols + c, x = c * CTU, y = r * CTU, w = std::min(CTU, cfg.pic_w - x), h = std::min(CTU, cfg.pic_h - y);
-          ShardRec& t = sendb[q++];
-          t.addr = a; t.valid = 1; t.cost = E.ctu_cost[a]; t.bits = E.ctu_bits[a]; t.dist = E.ctu_dist[a]; t.frac = E.ctu_rd_fraction[a]; t.entry = E.ctu_entry[a]; t.exit = E.ctu_exit[a];
-          memcpy(t.parts, &E.pic[(size_t)a * 256], sizeof(t.parts));
-          inner->export_block(x, y + cfg.y_origin, w, h, t.y, t.cb, t.cr);
-        }
-        cfg.shard->allgather(&sendb[0], &recvb[0], sizeof(ShardRec) * sendb.size());
-        bool any_cancel = false;
-        for (int g = 0; g < world; g++) {
-          const ShardRec* rr = &recvb[(size_t)g * (slots + 1)];
-          any_cancel |= rr[0].valid != 0;
-          if (g == rank) continue;
-          for (int k2 = 1; k2 <= slots; k2++) {
-            const ShardRec& t = rr[k2];
-            if (!t.valid) continue;
-            const int a = t.addr, c = a % cols, r = a / cols, x = c * CTU, y = r * CTU, w = std::min(CTU, cfg.pic_w - x), h = std::min(CTU, cfg.pic_h - y);
-            if (a < 0 || a >= E.n_ctu() || r % world != g) throw 1;
-            E.ctu_cost[a] = t.cost; E.ctu_bits[a] = t.bits; E.ctu_dist[a] = t.dist; E.ctu_rd_fraction[a] = (uint16_t)t.frac; E.ctu_entry[a] = t.entry; E.ctu_exit[a] = t.exit;
-            memcpy(&E.pic[(size_t)a * 256], t.parts, sizeof(t.parts));
-            for (int yy = y >> 3; yy < (y + h) >> 3; yy++) memset(&E.committed[(size_t)yy * (cfg.pic_w >> 3) + (x >> 3)], 1, w >> 3);
-            if (c == 1) ws.store_sync(0, r, t.exit);
-            inner->import_block(x, y + cfg.y_origin, w, h, t.y, t.cb, t.cr);
-          }
-        }
-        if (any_cancel) { ws.agreed_cancel.store(1); ws.steps_complete.store(ws.n_steps - 1); break; }   // every rank has seen it at this step: the rows stop at their next CTU
-        ws.steps_complete.store(s);
-      }
-    });
+    if (world > 1) pool.add([&]() { exchange_steps(E0, inner, pool, ws); });   // the exchange fiber
     run_t0 = std::chrono::steady_clock::now();
     pool.run(); pool.print_round_stats();
     rounds = pool.rounds; requests = pool.requests; serve_s = pool.serve_s;
@@ -1796,7 +1739,7 @@ void Encoder::wavefront_many(Encoder* const* encs, int n_pic, BatchInner* inner,
     std::vector<std::thread> th;
     run_t0 = std::chrono::steady_clock::now();
     for (int p = 0; p < n_pic; p++) for (int r = 0; r < rows; r++) th.emplace_back([&, p, r]() {
-      try { code_row(*encs[p], p, r, lane_of(p, r), lanes[(p * rows + r) % n_lanes], ws, init, [&](int st) { ws.wait(st); }, nullptr, cand[(size_t)p * rows + r]); }
+      try { code_row(*encs[p], p, r, lane_of(p, r), lanes[(p * rows + r) % n_lanes], ws, init, [&](int st) { ws.wait(st); }, cand[(size_t)p * rows + r]); }
       catch (...) {}                                                    // (code_row has recorded it in ws.error; rethrown below, after the join)
     });
     for (auto& t : th) t.join();

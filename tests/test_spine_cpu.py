@@ -240,42 +240,35 @@ def test_stacked_pictures_equal_the_pictures_alone(monkeypatch):
     assert rr[1] / rr[0] > 1.5                    # requests of both pictures met in the batches
 
 
-@pytest.mark.parametrize("slots", ["16"])
-def test_posted_requests_keep_every_result_and_save_rounds(slots, monkeypatch):
-    """HOP_SPINE_POSTED: requests without an answer (predictions, reconstructions put aside / brought back, commits) no longer stop their row; they are issued first whenever
-    requests are served.  The picture's candidates, costs, partition data, reconstruction, levels and the RD coder's fractions must be those of the reference run with
-    WaveFrontSynchro, and the rounds that served nothing else disappear (about a third of all rounds)."""
-    monkeypatch.setenv("HOP_SPINE_FUSE_PRED", "0")                  # (the mode's premise: predictions as requests of their own; fused into the evaluations they are no requests at all)
+def test_predictions_as_requests_of_their_own_keep_every_result(monkeypatch):
+    """HOP_SPINE_FUSE_PRED=0: a candidate's final predictions are requests of their own (RQ_PRED) instead of travelling inside its evaluation.  Either way the picture's
+    candidates, costs, partition data, reconstruction, levels and the RD coder's fractions must be those of the reference run with WaveFrontSynchro, and the two runs
+    equal each other; the predictions of their own are requests the default run does not issue."""
     L = spine_cpu()
     W, H, seed, lag = 192, 128, 7, 5
     Y, Cb, Cr = frame(W, H, seed, False)
     G = np.load(os.path.join(ROOT, "tests", "golden", "encoder_spine.npz"))
-    monkeypatch.setenv("HOP_SPEC_SLOTS", slots)
+    monkeypatch.setenv("HOP_SPEC_SLOTS", "16")
     out = {}
-    for posted in (("0", "1", "2") if slots == "16" else ("2",)):         # without candidate slots: the posted run against the reference's golden only
-        monkeypatch.setenv("HOP_SPINE_POSTED", posted)
+    for fuse in ("0", None):                                           # None: the default (fused)
+        if fuse is None: monkeypatch.delenv("HOP_SPINE_FUSE_PRED", raising=False)
+        else: monkeypatch.setenv("HOP_SPINE_FUSE_PRED", fuse)
         cost, bits, dist, parts, rec, text, rr = run_cpu_wpp(L, W, H, Y, Cb, Cr, lag)
         check_against_golden(G, key_of(W, H, seed, False) + "_wpp", cost, bits, dist, parts, text)
-        out[posted] = (cost, bits, dist, parts.tobytes(), [r.copy() for r in rec], cpu_last_levels(L, len(cost)), cpu_last_rd_fraction(L, len(cost)), rr.copy())
-    if slots != "16":
-        return
-    a = out["0"]
-    for lvl, share in (("1", 0.97), ("2", 0.75)):                      # 1: restore / commit posted (the most the device allows; the default is 0); 2: stash and predictions too
-        b = out[lvl]
-        assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2]) and a[3] == b[3]
-        assert all(np.array_equal(x, y) for x, y in zip(a[4], b[4])) and np.array_equal(a[5], b[5]) and np.array_equal(a[6], b[6])
-        assert a[7][1] <= b[7][1] <= 1.05 * a[7][1] and b[7][0] < share * a[7][0], (lvl, a[7], b[7])   # the same requests (posted: a decision's restore + commit count as two) in fewer rounds
-    print("rounds", a[7][0], "->", b[7][0], "requests", a[7][1])
+        out[fuse] = (cost, bits, dist, parts.tobytes(), [r.copy() for r in rec], cpu_last_levels(L, len(cost)), cpu_last_rd_fraction(L, len(cost)), rr.copy())
+    a, b = out["0"], out[None]
+    assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2]) and a[3] == b[3]
+    assert all(np.array_equal(x, y) for x, y in zip(a[4], b[4])) and np.array_equal(a[5], b[5]) and np.array_equal(a[6], b[6])
+    print("rounds", a[7][0], "->", b[7][0], "requests", a[7][1], "->", b[7][1])
+    assert a[7][1] > b[7][1], (a[7], b[7])                              # the mode's meaning: the predictions are requests
 
 
-def test_posted_requests_stacked_pictures(monkeypatch):
-    """the same with two pictures side by side on one rendezvous: each equals the picture coded alone"""
+def test_stacked_small_pictures_equal_the_pictures_alone():
+    """a second stack, without candidate slots: two one-row pictures side by side on one rendezvous, each equal to the picture coded alone"""
     L = spine_cpu()
     W, H, lag = 128, 64, 5
     pics = [frame(W, H, 1234, False), frame(W, H, 21, False)]
-    monkeypatch.setenv("HOP_SPINE_POSTED", "2")
     cost, bits, dist, parts, rec, rr = run_cpu_stack(L, W, H, pics, 64 + 320, lag)
-    monkeypatch.setenv("HOP_SPINE_POSTED", "0")
     for k, (Y, Cb, Cr) in enumerate(pics):
         c1, b1, d1, p1, r1, _, _ = run_cpu_wpp(L, W, H, Y, Cb, Cr, lag)
         assert np.array_equal(cost[k], c1) and np.array_equal(bits[k], b1) and np.array_equal(dist[k], d1) and parts[k].tobytes() == p1.tobytes() and np.array_equal(rec[k], r1[0]), k

@@ -1,5 +1,5 @@
 #!/bin/bash
-# restore / commit posted (stash not), the chain of first sub-CUs with their parent: the whole GPU suite, then the bench at 48 and 96 slots
+# the chain of first sub-CUs with their parent: the whole GPU suite, then the bench at 48 and 96 slots
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/r03; mkdir -p $O; cd $R
 timeout -k 10 1000 python -m pytest tests -m gpu -x -q > $O/t_w.log 2>&1 || { echo "GPU suite FAILED"; tail -n 25 $O/t_w.log; exit 1; }
 echo "gpu suite: $(tail -n 1 $O/t_w.log)"
