@@ -225,7 +225,7 @@ int hop_ctx_create_view_on(hop_ctx* parent, hipStream_t borrowed, hop_ctx** out)
   c->stride_y = parent->stride_y; c->stride_c = parent->stride_c; c->sub_h = parent->sub_h; c->sub_pitch = parent->sub_pitch; c->slots = parent->slots; c->fused_leaf_max = parent->fused_leaf_max; c->walk_max = parent->walk_max; c->ss_families = parent->ss_families; c->row_limit = parent->row_limit; c->lanes = 1; c->is_view = true;
   c->org_y = parent->org_y; c->org_cb = parent->org_cb; c->org_cr = parent->org_cr;
   for (int k = 0; k < 3; k++) { c->ss_alloc[k] = parent->ss_alloc[k]; c->ss_buf[k] = parent->ss_buf[k]; c->ss00[k] = parent->ss00[k]; c->pred[k] = parent->pred[k]; c->rec[k] = parent->rec[k]; }
-  c->entropy_bits = parent->entropy_bits; c->rdoq_scans = parent->rdoq_scans; c->have_orig = parent->have_orig; c->stash = parent->stash; c->stash_slots = parent->stash_slots; c->coefpic = parent->coefpic; c->coef_stash = parent->coef_stash;
+  c->entropy_bits = parent->entropy_bits; c->rdoq_scans = parent->rdoq_scans; c->have_orig = parent->have_orig; c->stash = parent->stash; c->stash_slots = parent->stash_slots; c->coefpic = parent->coefpic; c->coef_stash = parent->coef_stash; c->pic_qps = parent->pic_qps;
   hipError_t e = hipSetDevice(c->device);
   if (e == hipSuccess) e = create_lanes(c, hipStreamNonBlocking, false, borrowed);
   if (e != hipSuccess) { hop_set_err(parent, HOP_ERR_DEVICE, "hop_ctx_create_view_on: %s", hipGetErrorString(e)); hop_ctx_destroy(c); return HOP_ERR_DEVICE; }
@@ -250,6 +250,7 @@ int hop_ctx_create(hop_ctx** out, int pic_w, int pic_h, int bit_depth_y, int bit
   hop_ctx* c = (hop_ctx*)calloc(1, sizeof(hop_ctx));
   c->pic_w = pic_w; c->pic_h = pic_h; c->bd_y = bit_depth_y; c->bd_c = bit_depth_c; c->device = device;
   c->stride_y = pic_w + 2 * HOP_MARGIN_Y; c->stride_c = (pic_w >> 1) + 2 * HOP_MARGIN_C;
+  c->pic_qps = (hop_pic_qps*)calloc(1, sizeof(hop_pic_qps));
   { const char* f = getenv("HOP_FUSED_LEAF"); c->fused_leaf_max = f ? atoi(f) : 8192; }
   { const char* f = getenv("HOP_WALK"); c->walk_max = f ? atoi(f) : 4096; }               // developer switch: the results do not depend on it
   { const char* f = getenv("HOP_SS_FAMILIES"); c->ss_families = !(f && f[0] == '0'); }   // developer switch: the results do not depend on it
@@ -334,13 +335,29 @@ int hop_ctx_set_row_limit(hop_ctx* c, int on) {
   return HOP_OK;
 }
 
+static void clear_picture_qps(hop_ctx* c) { if (c->pic_qps) { free(c->pic_qps->qp); c->pic_qps->qp = nullptr; c->pic_qps->n = 0; } }
 int hop_stack_pitch(int sub_h) { return ((sub_h + 63) / 64) * 64 + 64 * ((2 * (HOP_MARGIN_Y + HOP_GUARD_ROWS) + 63) / 64); }
 int hop_ctx_set_stack(hop_ctx* c, int sub_h, int sub_pitch) {
   if (!c || c->is_view) return hop_set_err(c, HOP_ERR_ARG, "hop_ctx_set_stack: bad argument");
-  if (sub_h == 0 && sub_pitch == 0) { c->sub_h = c->sub_pitch = 0; return HOP_OK; }
+  if (sub_h == 0 && sub_pitch == 0) { c->sub_h = c->sub_pitch = 0; clear_picture_qps(c); return HOP_OK; }
   if (sub_h <= 0 || (sub_h & 7) || (sub_pitch & 63) || sub_pitch < hop_stack_pitch(sub_h) || c->pic_h < sub_h || (c->pic_h - sub_h) % sub_pitch)
     return hop_set_err(c, HOP_ERR_ARG, "hop_ctx_set_stack: a %d-row context is not a stack of %d-row pictures %d rows apart (pitch: a multiple of 64, at least hop_stack_pitch)", c->pic_h, sub_h, sub_pitch);
   c->sub_h = sub_h; c->sub_pitch = sub_pitch;
+  clear_picture_qps(c);                                                 // the picture count changes
+  return HOP_OK;
+}
+
+// One QP per picture of the context (include/hophip.h).  The table is the parent's; views read it through the pointer they copied (hop_picture_qps, hop_dev.h).
+int hop_ctx_set_picture_qps(hop_ctx* c, int32_t n, const int32_t* qp) {
+  if (!c || c->is_view || !c->pic_qps) return hop_set_err(c, HOP_ERR_ARG, "hop_ctx_set_picture_qps: bad argument (a view reads its parent's table)");
+  if (n == 0 && !qp) { clear_picture_qps(c); return HOP_OK; }
+  const int n_pic = hop_pictures(c, nullptr);
+  if (n != n_pic || !qp) return hop_set_err(c, HOP_ERR_ARG, "hop_ctx_set_picture_qps: %d QPs%s, the context holds %d picture%s", n, qp ? "" : " (NULL)", n_pic, n_pic > 1 ? "s" : "");
+  for (int k = 0; k < n; k++) if (qp[k] < 0 || qp[k] > 51) return hop_set_err(c, HOP_ERR_ARG, "hop_ctx_set_picture_qps: picture %d: qp %d is outside 0..51", k, qp[k]);
+  int32_t* t = (int32_t*)malloc(sizeof(int32_t) * (size_t)n);
+  if (!t) return hop_set_err(c, HOP_ERR_STATE, "hop_ctx_set_picture_qps: out of memory");
+  memcpy(t, qp, sizeof(int32_t) * (size_t)n);
+  free(c->pic_qps->qp); c->pic_qps->qp = t; c->pic_qps->n = n;
   return HOP_OK;
 }
 
@@ -353,6 +370,7 @@ void hop_ctx_destroy(hop_ctx* c) {
   }
   for (int i = 0; i < c->prof_cap; i++) { if (c->prof_recs[i].a) (void)hipEventDestroy(c->prof_recs[i].a); if (c->prof_recs[i].b) (void)hipEventDestroy(c->prof_recs[i].b); }
   free(c->prof_recs); free(c->rd_fraction);
+  if (c->pic_qps && !c->is_view) { free(c->pic_qps->qp); free(c->pic_qps); }
   void* ptrs[] = { c->org_y, c->org_cb, c->org_cr, c->ss_alloc[0], c->ss_alloc[1], c->ss_alloc[2], c->pred[0], c->pred[1], c->pred[2],
                    c->rec[0], c->rec[1], c->rec[2], c->scratch, c->stage, c->rqt_buf, c->walk_buf, c->rdoq_scans, c->entropy_bits, c->stash, c->coefpic, c->coef_stash };
   for (void* p : ptrs) if (p) (void)hipFree(p);

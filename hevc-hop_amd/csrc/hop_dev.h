@@ -1,6 +1,7 @@
 // hop_dev.h -- shared host/device declarations of libhophip (gfx950 only; wave = 64).
 #pragma once
 #include <atomic>
+#include <vector>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/hophip.h"
@@ -65,7 +66,19 @@ struct hop_ctx : hop_lane {
   double   prof_ms[HOP_K_COUNT];
   uint64_t prof_launches[HOP_K_COUNT], prof_units[HOP_K_COUNT];
   bool   levels_valid;               // coefpic holds the levels of the picture(s) the context holds: set by a hop_encode_frame that returned HOP_OK, cleared when one starts and by hop_decode_frame
+  struct hop_pic_qps* pic_qps;       // hop_ctx_set_picture_qps: the table of per-picture QPs, the parent's own object (a view points at its parent's, so it sees every later change)
 };
+struct hop_pic_qps { int n; int32_t* qp; };   // n == 0: no table set
+// the pictures of the context and the rows of one of them (hop_ctx_set_stack)
+static inline int hop_pictures(const hop_ctx* c, int* ph) {
+  if (ph) *ph = c->sub_pitch ? c->sub_h : c->pic_h;
+  return c->sub_pitch ? (c->pic_h - c->sub_h) / c->sub_pitch + 1 : 1;
+}
+// hop_ctx_set_picture_qps: the table (one QP per picture of the context), or NULL while none is set.  A table whose length is not the picture count -- a view made
+// before its parent was stacked counts its pictures differently -- reads as none.
+static inline const int32_t* hop_picture_qps(const hop_ctx* c) {
+  return (c->pic_qps && c->pic_qps->n > 0 && c->pic_qps->n == hop_pictures(c, nullptr)) ? c->pic_qps->qp : nullptr;
+}
 struct hop_prof_rec { hipEvent_t a, b; int kernel; uint64_t units; };
 int  hop_prof_begin(hop_ctx* c, int kernel, uint64_t units);   // returns record index or -1 when profiling is off
 void hop_prof_end(hop_ctx* c, int rec);
@@ -249,6 +262,8 @@ int hop_launch_coeff_bits(hop_ctx* c, int n, const hop_coeff_bits_job* d_jobs, c
 int hop_launch_ssref_reset(hop_ctx* c);
 int hop_launch_ssref_commit(hop_ctx* c, int n, const int32_t* d_rect4, const int16_t* d_y, const int16_t* d_cb, const int16_t* d_cr, int packed);
 int hop_set_err(hop_ctx* c, int code, const char* fmt, ...);
+// csrc/k_entropy.hip: the initial context models of a slice-data call, one table of EN_STATES bytes per distinct QP among pic_qp[0 .. n_pic) (NULL: one table at qp)
+int hop_ent_init_tables(int slice_type, int qp, const int32_t* pic_qp, int n_pic, std::vector<uint8_t>& tabs, std::vector<int32_t>& init_of);
 int hop_scratch(hop_ctx* c, size_t bytes, void** out);
 // hop_ctx_create_view's internal form (k_spine.hip: the buffer sets of the candidate evaluations): the view works on `borrowed`, a stream made by hop_view_stream_create
 // that it does not destroy, and hop_view_set_stream moves it -- a view with nothing queued -- to another such stream.  hop_view_stream_create makes the stream a view of

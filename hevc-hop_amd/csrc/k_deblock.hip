@@ -12,7 +12,8 @@
 //                    segments along a sample row, so a wave's loads are contiguous (vertical edges: 16 B per thread per row; horizontal: 8 B per thread per row)
 //   k_dbk_chroma<DIR> one thread per segment and plane on the 8-sample chroma grid, strength 2 only
 // all vertical edges of the picture first, then all horizontal ones on the result, as loopFilterPic does.  HBM-bound: the planes are read and written once per direction
-// (2 x 2 x 3 B/sample) plus the partition data (44 B per 16 samples); DESIGN.md section 4 has the figures.  The pictures of a stacked context are blockIdx.z.
+// (2 x 2 x 3 B/sample) plus the partition data (44 B per 16 samples); DESIGN.md section 4 has the figures.  The pictures of a stacked context are blockIdx.z, and tc /
+// beta / the chroma QP come from the QP of the edge's own picture (dbk_qp: a table indexed by blockIdx.z, wave-uniform, so a scalar load).
 #include "hop_dev.h"
 
 #define HIPCHK(c, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return hop_set_err((c), HOP_ERR_DEVICE, "%s: %s", #call, hipGetErrorString(e_)); } while (0)
@@ -22,12 +23,14 @@ struct DbkGeo {
   int pitch_rows;                 // rows between the pictures of a stack in the reconstruction planes
   int w4, h4;                     // the picture in 4x4 units
   int qp, beta_off, tc_off, cb_off, cr_off, bd, disable;
+  const int32_t* pic_qp;          // one QP per picture of the stack, or NULL: qp for all of them
 };
 
 __constant__ uint8_t c_dbk_tc[54] = { 0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,1,1,1,1,1,1,1,1,1,2,2,2,2,3,3,3,3,4,4,4,5,5,6,6,7,8,9,10,11,13,14,16,18,20,22,24 };          // sm_tcTable :59-62
 __constant__ uint8_t c_dbk_beta[52] = { 0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,6,7,8,9,10,11,12,13,14,15,16,17,18,20,22,24,26,28,30,32,34,36,38,40,42,44,46,48,50,52,54,56,58,60,62,64 };   // sm_betaTable :64-67
 __constant__ uint8_t c_dbk_cqp[58] = { 0,1,2,3,4,5,6,7,8,9,10,11,12,13,14,15,16,17,18,19,20,21,22,23,24,25,26,27,28,29,29,30,31,32,33,33,34,34,35,35,36,36,37,37,38,39,40,41,42,43,44,45,46,47,48,49,50,51 };  // g_aucChromaScale
 
+__device__ __forceinline__ int dbk_qp(const DbkGeo& g, int pic) { return g.pic_qp ? g.pic_qp[pic] : g.qp; }
 __device__ __forceinline__ int dbk_clip3(int lo, int hi, int v) { return v < lo ? lo : v > hi ? hi : v; }
 __device__ __forceinline__ int dbk_z(int ux, int uy) {   // z-order index of unit (ux, uy) inside a CTU
   return (ux & 1) | ((uy & 1) << 1) | ((ux & 2) << 1) | ((uy & 2) << 2) | ((ux & 4) << 2) | ((uy & 4) << 3) | ((ux & 8) << 3) | ((uy & 8) << 4);
@@ -105,7 +108,8 @@ __global__ __launch_bounds__(256) void k_dbk_luma(DbkGeo g, const uint8_t* __res
   const int bs = bs_plane[(size_t)pic * g.w4 * g.h4 + (size_t)y4 * g.w4 + x4];
   if (!bs) return;
   const int scale = 1 << (g.bd - 8), maxv = (1 << g.bd) - 1;
-  const int tc = c_dbk_tc[dbk_clip3(0, 53, g.qp + 2 * (bs - 1) + (g.tc_off << 1))] * scale, beta = c_dbk_beta[dbk_clip3(0, 51, g.qp + (g.beta_off << 1))] * scale;
+  const int qp = dbk_qp(g, pic);
+  const int tc = c_dbk_tc[dbk_clip3(0, 53, qp + 2 * (bs - 1) + (g.tc_off << 1))] * scale, beta = c_dbk_beta[dbk_clip3(0, 51, qp + (g.beta_off << 1))] * scale;
   int16_t* base = rec + ((size_t)pic * g.pitch_rows + (size_t)y4 * 4) * g.w + x4 * 4;
   int s[4][8];
   if (DIR == 0) {
@@ -148,7 +152,7 @@ __global__ __launch_bounds__(256) void k_dbk_chroma(DbkGeo g, const uint8_t* __r
   const int bs = bs_plane[(size_t)pic * g.w4 * g.h4 + (size_t)y4 * g.w4 + x4];
   if (bs < 2) return;
   const int wc = g.w >> 1, scale = 1 << (g.bd - 8), maxv = (1 << g.bd) - 1;
-  const int qi = g.qp + (comp == 0 ? g.cb_off : g.cr_off), qpc = qi < 0 ? qi : qi > 57 ? qi - 6 : c_dbk_cqp[qi];                     // QpUV :53
+  const int qi = dbk_qp(g, pic) + (comp == 0 ? g.cb_off : g.cr_off), qpc = qi < 0 ? qi : qi > 57 ? qi - 6 : c_dbk_cqp[qi];                     // QpUV :53
   const int tc = c_dbk_tc[dbk_clip3(0, 53, qpc + 2 * (bs - 1) + (g.tc_off << 1))] * scale;
   int16_t* base = (comp == 0 ? cb : cr) + ((size_t)pic * (g.pitch_rows >> 1) + (size_t)y4 * 2) * wc + x4 * 2;
   const ptrdiff_t o = DIR == 0 ? 1 : wc, step = DIR == 0 ? wc : 1;
@@ -161,12 +165,15 @@ __global__ __launch_bounds__(256) void k_dbk_chroma(DbkGeo g, const uint8_t* __r
   }
 }
 
-extern "C" int hop_deblock_frame(hop_ctx* c, const hop_deblock_params* p, const hop_cu_part* parts) {
+// internal: hop_deblock_frame with the QP of every picture handed down -- pic_qp (host, one per picture of the context) or NULL: p->qp for all.  hop_deblock_frame passes
+// the context's table (hop_ctx_set_picture_qps); hop_access_unit_decode and hop_access_units_decode (csrc/k_stream.hip) pass the QPs their streams carry.
+extern "C" __attribute__((visibility("hidden"))) int hop_dbk_device(hop_ctx* c, const hop_deblock_params* p, const hop_cu_part* parts, const int32_t* pic_qp) {
   if (!c || !p || !parts) return hop_set_err(c, HOP_ERR_ARG, "hop_deblock_frame: bad argument");
   if (c->bd_y != c->bd_c) return hop_set_err(c, HOP_ERR_ARG, "hop_deblock_frame: luma and chroma bit depths must be equal");
   if (p->qp < 0 || p->qp > 51 || p->beta_offset_div2 < -6 || p->beta_offset_div2 > 6 || p->tc_offset_div2 < -6 || p->tc_offset_div2 > 6 || p->cb_qp_offset < -12 || p->cb_qp_offset > 12 ||
       p->cr_qp_offset < -12 || p->cr_qp_offset > 12) return hop_set_err(c, HOP_ERR_ARG, "hop_deblock_frame: parameter out of range");
   const int n_pic = c->sub_pitch ? (c->pic_h - c->sub_h) / c->sub_pitch + 1 : 1, h = c->sub_pitch ? c->sub_h : c->pic_h;
+  if (pic_qp) for (int k = 0; k < n_pic; k++) if (pic_qp[k] < 0 || pic_qp[k] > 51) return hop_set_err(c, HOP_ERR_ARG, "hop_deblock_frame: picture %d: qp %d out of range", k, pic_qp[k]);
   if ((c->pic_w & 7) || (h & 7)) return hop_set_err(c, HOP_ERR_ARG, "hop_deblock_frame: the picture size must be a multiple of the minimum CU size (8)");
   DbkGeo g;
   g.w = c->pic_w; g.h = h; g.wctu = (g.w + 63) >> 6; g.n_ctu = g.wctu * ((h + 63) >> 6); g.pitch_rows = c->sub_pitch; g.w4 = g.w >> 2; g.h4 = h >> 2;
@@ -175,8 +182,11 @@ extern "C" int hop_deblock_frame(hop_ctx* c, const hop_deblock_params* p, const 
   const size_t n_parts = (size_t)n_pic * g.n_ctu * 256, n_units = (size_t)n_pic * g.w4 * g.h4;
   hop_cu_part* d_parts = nullptr; uint8_t* d_bs = nullptr;
   HIPCHK(c, hipMalloc((void**)&d_parts, n_parts * sizeof(hop_cu_part)));
-  hipError_t e = hipMalloc((void**)&d_bs, 2 * n_units);
+  const size_t o_qp = (2 * n_units + 3) & ~(size_t)3;                     // the pictures' QPs behind the two strength planes
+  hipError_t e = hipMalloc((void**)&d_bs, o_qp + (pic_qp ? sizeof(int32_t) * (size_t)n_pic : 0));
   if (e == hipSuccess) e = hipMemcpyAsync(d_parts, parts, n_parts * sizeof(hop_cu_part), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess && pic_qp) e = hipMemcpyAsync(d_bs + o_qp, pic_qp, sizeof(int32_t) * (size_t)n_pic, hipMemcpyHostToDevice, c->stream);
+  g.pic_qp = (pic_qp && d_bs) ? (const int32_t*)(d_bs + o_qp) : nullptr;
   if (e == hipSuccess) {
     const unsigned units = (unsigned)(g.w4 * g.h4);
     const int rec_k = hop_prof_begin(c, HOP_K_DEBLOCK, (uint64_t)n_pic * g.n_ctu);
@@ -192,4 +202,8 @@ extern "C" int hop_deblock_frame(hop_ctx* c, const hop_deblock_params* p, const 
   (void)hipFree(d_parts); (void)hipFree(d_bs);
   if (e != hipSuccess) return hop_set_err(c, HOP_ERR_DEVICE, "hop_deblock_frame: %s", hipGetErrorString(e));
   return HOP_OK;
+}
+
+extern "C" int hop_deblock_frame(hop_ctx* c, const hop_deblock_params* p, const hop_cu_part* parts) {
+  return hop_dbk_device(c, p, parts, c ? hop_picture_qps(c) : nullptr);
 }

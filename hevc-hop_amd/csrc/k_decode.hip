@@ -74,14 +74,15 @@ struct DecArgs {
   hop_pics pic;                                // org = null: the intra setup reads no original
   hop_pics pic_tu;                             // org = the prediction planes: the TU bodies' distortion side output reads valid memory and is thrown away
   int16_t* rec[3]; int16_t* ss00[3];
-  int wctu, qp_scaled[3];
+  int wctu;
+  const int32_t* qp_scaled;                    // per picture: what setQPforQuant hands to setQpParam for Y, Cb, Cr (3 values each)
   int commit;                                  // an ISS slice commits every CU to the SS reference; an I slice has none
   int n_ctu, sub_h, sub_pitch;                 // the stack: CTUs and rows of one picture, the pictures' origins sub_pitch rows apart (0: one picture of sub_h rows)
 };
-struct DecPic { int top, bottom; };            // the first row of the CTU's picture and the first row below it, in the rows of the stack
+struct DecPic { int top, bottom; const int32_t* qp_scaled; };   // the first row of the CTU's picture and the first row below it, in the rows of the stack; its three scaled QPs
 
 // one TU of one plane: reconstruction = clip(prediction + inverse residual), or the prediction for cbf 0.  (x, y) in luma samples, log2 in this plane's samples
-__device__ void dec_tu(DecShared& sh, const DecArgs& A, int comp, int x, int y, int log2, bool cbf, bool tskip, bool dst, const int32_t* lv) {
+__device__ void dec_tu(DecShared& sh, const DecArgs& A, const DecPic& pp, int comp, int x, int y, int log2, bool cbf, bool tskip, bool dst, const int32_t* lv) {
   const int tid = threadIdx.x, N = 1 << log2;
   const bool chroma = comp != 0;
   const int pitch = chroma ? A.pic.pic_w >> 1 : A.pic.pic_w, x0 = chroma ? x >> 1 : x, y0 = chroma ? y >> 1 : y;
@@ -94,7 +95,7 @@ __device__ void dec_tu(DecShared& sh, const DecArgs& A, int comp, int x, int y, 
   }
   if (tid == 0) {
     hop_tu_rd_job j; memset(&j, 0, sizeof(j));
-    j.x = x; j.y = y; j.comp = comp; j.log2_size = log2; j.qp_scaled = A.qp_scaled[comp]; j.bit_depth = chroma ? A.pic.bd_c : A.pic.bd_y;
+    j.x = x; j.y = y; j.comp = comp; j.log2_size = log2; j.qp_scaled = pp.qp_scaled[comp]; j.bit_depth = chroma ? A.pic.bd_c : A.pic.bd_y;
     j.is_intra = 1;                                                    // the bodies' reconstruction path: clip(prediction + residual) into the picture
     j.use_dst = dst ? 1 : 0; j.flags = tskip ? HOP_TU_RD_TS : 0;
     sh.tj = j; sh.coef_off = 0; sh.abs_sum = 1;
@@ -118,7 +119,7 @@ __device__ void dec_intra_cu(DecShared& sh, const DecArgs& A, DecPic pp, const h
     __syncthreads();
     intra_pred_body(sh.u.in, &sh.ij, q.luma_dir, A.pic, A.rec[0]);
     __syncthreads();
-    dec_tu(sh, A, 0, x, y, l2, (q.cbf[0] >> q.tr_idx) & 1, q.tskip[0] != 0, l2 == 2, LV + 16 * (z + u));
+    dec_tu(sh, A, pp, 0, x, y, l2, (q.cbf[0] >> q.tr_idx) & 1, q.tskip[0] != 0, l2 == 2, LV + 16 * (z + u));
     u += tn;
   }
   int cm = P[z].chroma_dir;
@@ -136,7 +137,7 @@ __device__ void dec_intra_cu(DecShared& sh, const DecArgs& A, DecPic pp, const h
     for (int comp = 1; comp < 3; comp++) {
       intra_pred_chroma_body(sh.u.in, &sh.ij, cm, comp, A.pic, A.rec[1], A.rec[2]);
       __syncthreads();
-      dec_tu(sh, A, comp, x, y, lc, (q.cbf[comp] >> bit) & 1, q.tskip[comp] != 0, false, LV + (comp == 1 ? 4096 : 5120) + 4 * (z + u));
+      dec_tu(sh, A, pp, comp, x, y, lc, (q.cbf[comp] >> bit) & 1, q.tskip[comp] != 0, false, LV + (comp == 1 ? 4096 : 5120) + 4 * (z + u));
     }
     u += tn;
   }
@@ -183,11 +184,11 @@ __device__ void dec_inter_cu(DecShared& sh, const DecArgs& A, DecPic pp, const h
     const int l2 = log2cu - q.tr_idx, tn = 1 << (2 * (l2 - 2));
     int x4, y4; dec_zpos(z + u, x4, y4);
     const int x = (cx & ~63) + 4 * x4, y = (cy & ~63) + 4 * y4;
-    dec_tu(sh, A, 0, x, y, l2, (q.cbf[0] >> q.tr_idx) & 1, q.tskip[0] != 0, false, LV + 16 * (z + u));
+    dec_tu(sh, A, pp, 0, x, y, l2, (q.cbf[0] >> q.tr_idx) & 1, q.tskip[0] != 0, false, LV + 16 * (z + u));
     if (l2 > 2 || ((z + u) & 3) == 0) {
       const int lc = l2 > 2 ? l2 - 1 : 2, bit = l2 > 2 ? q.tr_idx : q.tr_idx - 1;
       for (int comp = 1; comp < 3; comp++)
-        dec_tu(sh, A, comp, x, y, lc, (q.cbf[comp] >> bit) & 1, q.tskip[comp] != 0, false, LV + (comp == 1 ? 4096 : 5120) + 4 * (z + u));
+        dec_tu(sh, A, pp, comp, x, y, lc, (q.cbf[comp] >> bit) & 1, q.tskip[comp] != 0, false, LV + (comp == 1 ? 4096 : 5120) + 4 * (z + u));
     }
     u += tn;
   }
@@ -197,7 +198,7 @@ __global__ __launch_bounds__(256) void k_dec_ctu(DecArgs A) {
   __shared__ DecShared sh;
   const int ctu = A.order[blockIdx.x];                                 // picture * n_ctu + the CTU's raster address in its picture
   const int k = ctu / A.n_ctu, a = ctu - k * A.n_ctu;
-  const DecPic pp = { k * A.sub_pitch, k * A.sub_pitch + A.sub_h };
+  const DecPic pp = { k * A.sub_pitch, k * A.sub_pitch + A.sub_h, A.qp_scaled + 3 * k };   // (k is the block's: a scalar address)
   const int cx0 = (a % A.wctu) * 64, cy0 = pp.top + (a / A.wctu) * 64;  // addressing stays absolute: rows of the stack
   const hop_cu_part* P = A.parts + (size_t)ctu * 256;
   const int32_t* LV = A.levels + (size_t)ctu * 6144;
@@ -232,9 +233,10 @@ static int dec_pictures(const hop_ctx* c, int* ph) {
 // internal: what hop_decode_frame, hop_decode_stack and hop_access_units_decode (csrc/k_stream.hip) share -- the checks, the plan of every picture of the context
 // (from the host parts; nothing is enqueued before it stands), the reset of the SS reference and one launch per level, picture k's CTUs at [k * n_ctu, (k + 1) * n_ctu).
 // d_parts == NULL: parts and `levels` (host) are uploaded into the scratch area.  Otherwise both are on the device already -- d_parts, d_levels, and d_order with room
-// for one int32 per CTU of the stack, in memory the caller keeps in place until this returns -- and `levels` is not read.  Synchronous.
+// for one int32 per CTU of the stack and three per picture (the scaled QPs go behind the order), in memory the caller keeps in place until this returns -- and `levels`
+// is not read.  pic_qp (host, one per picture of the context) or NULL: p->qp for all pictures.  Synchronous.
 extern "C" __attribute__((visibility("hidden"))) int hop_dec_device(hop_ctx* c, const char* who, const char* noun, const hop_dec_params* p, const hop_cu_part* parts, const int32_t* levels,
-                                                                    const hop_cu_part* d_parts, const int32_t* d_levels, int32_t* d_order) {
+                                                                    const hop_cu_part* d_parts, const int32_t* d_levels, int32_t* d_order, const int32_t* pic_qp) {
   if (c->shard_world > 1) return hop_set_err(c, HOP_ERR_ARG, "%s: a sharded context decodes no picture", who);
   if (p->schedule != 0 && p->schedule != 1) return hop_set_err(c, HOP_ERR_ARG, "%s: schedule %d", who, p->schedule);
   if (p->plain_intra != 0 && p->plain_intra != 1) return hop_set_err(c, HOP_ERR_ARG, "%s: plain_intra %d", who, p->plain_intra);
@@ -259,16 +261,21 @@ extern "C" __attribute__((visibility("hidden"))) int hop_dec_device(hop_ctx* c, 
   static const uint8_t chroma_scale[58] = { 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29,
                                             29, 30, 31, 32, 33, 33, 34, 34, 35, 35, 36, 36, 37, 37, 38, 39, 40, 41, 42, 43, 44, 45, 46, 47, 48, 49, 50, 51 };
   DecArgs A;
-  A.qp_scaled[0] = p->qp + off_y;
-  for (int k = 1; k < 3; k++) {
-    const int o = k == 1 ? p->cb_qp_offset : p->cr_qp_offset;
-    const int q = std::min(57, std::max(-off_c, p->qp + o));
-    A.qp_scaled[k] = q < 0 ? q + off_c : chroma_scale[q] + off_c;
+  std::vector<int32_t> qs(3 * (size_t)n_pic);
+  for (int i = 0; i < n_pic; i++) {
+    const int qp = pic_qp ? pic_qp[i] : p->qp;
+    if (qp < -off_y || qp > 51) return hop_set_err(c, HOP_ERR_ARG, "%s: %s %d: qp %d out of range", who, noun, i, qp);
+    qs[3 * i] = qp + off_y;
+    for (int k = 1; k < 3; k++) {
+      const int o = k == 1 ? p->cb_qp_offset : p->cr_qp_offset;
+      const int q = std::min(57, std::max(-off_c, qp + o));
+      qs[3 * i + k] = q < 0 ? q + off_c : chroma_scale[q] + off_c;
+    }
   }
   hipError_t e = hipSetDevice(c->device);
   if (!d_parts) {                                                       // parts and levels from the host: uploaded once, the order behind them
     const size_t b_parts = sizeof(hop_cu_part) * 256 * (size_t)n, b_levels = sizeof(int32_t) * 6144 * (size_t)n;
-    const size_t o_levels = (b_parts + 255) & ~(size_t)255, o_order = (o_levels + b_levels + 255) & ~(size_t)255, total = o_order + sizeof(int32_t) * (size_t)n;
+    const size_t o_levels = (b_parts + 255) & ~(size_t)255, o_order = (o_levels + b_levels + 255) & ~(size_t)255, total = o_order + sizeof(int32_t) * ((size_t)n + 3 * (size_t)n_pic);
     void* buf; const int r = hop_scratch(c, total, &buf); if (r) return r;
     char* b = (char*)buf;
     if (e == hipSuccess) e = hipMemcpyAsync(b, parts, b_parts, hipMemcpyHostToDevice, c->stream);
@@ -276,6 +283,8 @@ extern "C" __attribute__((visibility("hidden"))) int hop_dec_device(hop_ctx* c, 
     d_parts = (const hop_cu_part*)b; d_levels = (const int32_t*)(b + o_levels); d_order = (int32_t*)(b + o_order);
   }
   if (e == hipSuccess) e = hipMemcpyAsync(d_order, order.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_order + n, qs.data(), sizeof(int32_t) * qs.size(), hipMemcpyHostToDevice, c->stream);
+  A.qp_scaled = d_order + n;
   if (e != hipSuccess) return hop_set_err(c, HOP_ERR_DEVICE, "%s: upload: %s", who, hipGetErrorString(e));
   if (!p->plain_intra) { const int r = hop_launch_ssref_reset(c); if (r) return r; }
   A.parts = d_parts; A.levels = d_levels;
@@ -297,12 +306,12 @@ extern "C" __attribute__((visibility("hidden"))) int hop_dec_device(hop_ctx* c, 
 extern "C" int hop_decode_frame(hop_ctx* c, const hop_dec_params* p, const hop_cu_part* parts, const int32_t* levels) {
   if (!c || !p || !parts || !levels) return hop_set_err(c, HOP_ERR_ARG, "hop_decode_frame: bad argument");
   if (c->sub_pitch || c->sub_h) return hop_set_err(c, HOP_ERR_ARG, "hop_decode_frame: a stacked context decodes no picture (one picture per context)");
-  return hop_dec_device(c, "hop_decode_frame", "picture", p, parts, levels, nullptr, nullptr, nullptr);
+  return hop_dec_device(c, "hop_decode_frame", "picture", p, parts, levels, nullptr, nullptr, nullptr, nullptr);
 }
 
 extern "C" int hop_decode_stack(hop_ctx* c, const hop_dec_params* p, const hop_cu_part* parts, const int32_t* levels) {
   if (!c || !p || !parts || !levels) return hop_set_err(c, HOP_ERR_ARG, "hop_decode_stack: bad argument");
-  return hop_dec_device(c, "hop_decode_stack", "picture", p, parts, levels, nullptr, nullptr, nullptr);
+  return hop_dec_device(c, "hop_decode_stack", "picture", p, parts, levels, nullptr, nullptr, nullptr, hop_picture_qps(c));
 }
 
 // host only; defined here, not in host/hop_decode.cpp, because the reason of a refusal goes where hop_last_error(NULL) reads it

@@ -10,7 +10,8 @@
 // with both barriers outside lane-divergent code.  Without wpp one launch and one wave per picture walk all CTUs.
 //   k_parse_init   every unit of the outputs as an unparsed one (what a substream that stops early leaves behind)
 //   k_parse_diag   one wave per active row: load, one CTU, store; the models after CTU 1 become the next row's entry state
-// No kernel looks at another workgroup's progress.
+// No kernel looks at another workgroup's progress.  As in the writer, the pictures of a stack may differ in their slice QP: one table of initial models per distinct QP,
+// and a picture's rows start from the table init_of names for it (indexed by the block's picture, wave-uniform).
 #include <algorithm>
 #include <vector>
 #include "hop_dev.h"
@@ -27,11 +28,11 @@ int hop_ent_init_states(uint8_t st[EN_STATES], int slice_type, int qp);         
 int hop_parse_check(int pic_w, int pic_h, int bit_depth, int n_pic, const hop_slice_data_params* p, const uint8_t* data, const uint32_t* substream_bytes, int n_substreams,
                     const hop_cu_part* parts, const hop_sao_param* sao, size_t* total, char* err, size_t errn);     // host/hop_parse.cpp
 __attribute__((visibility("hidden"))) int hop_parse_device(hop_ctx* c, const hop_slice_data_params* p, const uint8_t* data, const uint8_t* d_data, const uint32_t* substream_bytes,
-                                                           int32_t n_substreams, hop_cu_part* parts, int32_t* levels, hop_sao_param* sao, size_t front);
+                                                           int32_t n_substreams, hop_cu_part* parts, int32_t* levels, hop_sao_param* sao, size_t front, const int32_t* pic_qp);
 struct hop_parse_where { const hop_cu_part* d_parts; const int32_t* d_levels; size_t end; };   // where the parser left its outputs on the device; the end of its work area
 __attribute__((visibility("hidden"))) int hop_parse_device_at(hop_ctx* c, const char* who, const char* noun, const hop_slice_data_params* p, const uint8_t* data, const uint8_t* d_data,
                                                               const unsigned long long* offsets, const uint32_t* substream_bytes, int32_t n_substreams, hop_cu_part* parts,
-                                                              int32_t* levels, hop_sao_param* sao, size_t front, hop_parse_where* where);
+                                                              int32_t* levels, hop_sao_param* sao, size_t front, hop_parse_where* where, const int32_t* pic_qp);
 }
 
 namespace {
@@ -39,7 +40,8 @@ struct ParState { uint32_t range, value; int32_t bits_needed; uint32_t pos, flag
 struct ParArgs {
   ParPic pic;                      // parts / levels / sao: picture 0's
   int32_t n_pic, n_sub;
-  const uint8_t* init;             // EN_STATES: the initial context models
+  const uint8_t* init;             // EN_STATES per distinct QP: the initial context models
+  const int32_t* init_of;          // per picture: which of them (NULL: one QP, table 0)
   uint8_t* entry;                  // wpp: EN_STATES per CTU row of every picture
   const uint8_t* data; const unsigned long long* offs; const uint32_t* sizes;   // per substream: where its bytes start, how many they are
   ParState* state;                 // per substream
@@ -70,7 +72,7 @@ __global__ __launch_bounds__(64) void k_parse_diag(ParArgs A, int d, int r0, int
   ParState& S = A.state[sub];
   uint32_t* st = (uint32_t*)k.st;
   if (col == 0) {                                                         // a picture one CTU wide has no CTU above right: every row starts from the initial models
-    const uint32_t* e = (const uint32_t*)((r == 0 || g.e.wctu < 2) ? A.init : A.entry + ((size_t)pic * g.e.hctu + r) * EN_STATES);
+    const uint32_t* e = (const uint32_t*)((r == 0 || g.e.wctu < 2) ? (A.init_of ? A.init + (size_t)A.init_of[pic] * EN_STATES : A.init) : A.entry + ((size_t)pic * g.e.hctu + r) * EN_STATES);
     if (t < EN_STATES / 4) st[t] = e[t];
   } else if (t < EN_STATES / 4) st[t] = S.st[t];
   __syncthreads();
@@ -95,13 +97,13 @@ __global__ __launch_bounds__(64) void k_parse_diag(ParArgs A, int d, int r0, int
 }  // namespace
 
 // the work area: the outputs, the models, the substreams' places and states, and (when the data comes from the host) the data
-struct ParLayout { size_t o_parts, o_levels, o_sao, o_init, o_entry, o_offs, o_sizes, o_state, o_data, end; };
-static ParLayout par_layout(size_t front, int n_pic, int n, int hctu, int n_blocks, bool with_levels, bool with_sao, size_t own_data) {
+struct ParLayout { size_t o_parts, o_levels, o_sao, o_init, o_init_of, o_entry, o_offs, o_sizes, o_state, o_data, end; };
+static ParLayout par_layout(size_t front, int n_pic, int n, int hctu, int n_blocks, bool with_levels, bool with_sao, size_t own_data, int n_init /* tables of initial models */) {
   ParLayout L;
   size_t end = front;
   auto seg = [&](size_t bytes) { const size_t at = (end + 255) & ~(size_t)255; end = at + bytes; return at; };
   L.o_parts = seg(sizeof(hop_cu_part) * 256 * (size_t)n * n_pic); L.o_levels = seg(with_levels ? sizeof(int32_t) * 6144 * (size_t)n * n_pic : 0);
-  L.o_sao = seg(with_sao ? sizeof(hop_sao_param) * 3 * (size_t)n * n_pic : 0); L.o_init = seg(EN_STATES); L.o_entry = seg((size_t)n_pic * hctu * EN_STATES);
+  L.o_sao = seg(with_sao ? sizeof(hop_sao_param) * 3 * (size_t)n * n_pic : 0); L.o_init = seg((size_t)n_init * EN_STATES); L.o_init_of = seg(sizeof(int32_t) * (size_t)n_pic); L.o_entry = seg((size_t)n_pic * hctu * EN_STATES);
   L.o_offs = seg(sizeof(unsigned long long) * n_blocks); L.o_sizes = seg(sizeof(uint32_t) * n_blocks); L.o_state = seg(sizeof(ParState) * n_blocks); L.o_data = seg(own_data);
   L.end = end;
   return L;
@@ -111,20 +113,21 @@ static ParLayout par_layout(size_t front, int n_pic, int n, int hctu, int n_bloc
 extern "C" __attribute__((visibility("hidden"))) size_t hop_parse_work_bytes(const hop_ctx* c, size_t data_bytes, int n_substreams) {
   const int n_pic = c->sub_pitch ? (c->pic_h - c->sub_h) / c->sub_pitch + 1 : 1, ph = c->sub_pitch ? c->sub_h : c->pic_h;
   const int wctu = (c->pic_w + 63) / 64, hctu = (ph + 63) / 64;
-  return par_layout(0, n_pic, wctu * hctu, hctu, n_pic * n_substreams, true, true, data_bytes + 256).end + 256;
+  return par_layout(0, n_pic, wctu * hctu, hctu, n_pic * n_substreams, true, true, data_bytes + 256, n_pic).end + 256;   // (at most one table of initial models per picture)
 }
 
 extern "C" int hop_slice_data_parse(hop_ctx* c, const hop_slice_data_params* p, const uint8_t* data, const uint32_t* substream_bytes, int32_t n_substreams,
                                     hop_cu_part* parts, int32_t* levels, hop_sao_param* sao) {
   if (!c || !p || !data || !substream_bytes || !parts) return hop_set_err(c, HOP_ERR_ARG, "hop_slice_data_parse: bad argument");
-  return hop_parse_device(c, p, data, nullptr, substream_bytes, n_substreams, parts, levels, sao, 0);
+  return hop_parse_device(c, p, data, nullptr, substream_bytes, n_substreams, parts, levels, sao, 0, hop_picture_qps(c));
 }
 
 // internal: the parser over substreams that are on the host (data) or already on the device (d_data, inside the first `front` bytes of the context's scratch area, which
-// the caller sized with hop_parse_work_bytes so that it does not move here): hop_access_unit_decode hands over what its compact kernel wrote
+// the caller sized with hop_parse_work_bytes so that it does not move here): hop_access_unit_decode hands over what its compact kernel wrote.  pic_qp (host, one per
+// picture of the context) or NULL: p->qp for all pictures
 extern "C" __attribute__((visibility("hidden"))) int hop_parse_device(hop_ctx* c, const hop_slice_data_params* p, const uint8_t* data, const uint8_t* d_data, const uint32_t* substream_bytes, int32_t n_substreams,
-                                hop_cu_part* parts, int32_t* levels, hop_sao_param* sao, size_t front) {
-  return hop_parse_device_at(c, "hop_slice_data_parse", "picture", p, data, d_data, nullptr, substream_bytes, n_substreams, parts, levels, sao, front, nullptr);
+                                hop_cu_part* parts, int32_t* levels, hop_sao_param* sao, size_t front, const int32_t* pic_qp) {
+  return hop_parse_device_at(c, "hop_slice_data_parse", "picture", p, data, d_data, nullptr, substream_bytes, n_substreams, parts, levels, sao, front, nullptr, pic_qp);
 }
 
 // internal: the same with the substreams wherever they lie -- offsets (host, may be NULL: back to back): where substream i starts, counted from d_data, all of it inside
@@ -133,7 +136,7 @@ extern "C" __attribute__((visibility("hidden"))) int hop_parse_device(hop_ctx* c
 // only for a caller who asks.  who / noun: how an error names the entry and a picture ("picture", "access unit").
 extern "C" __attribute__((visibility("hidden"))) int hop_parse_device_at(hop_ctx* c, const char* who, const char* noun, const hop_slice_data_params* p, const uint8_t* data, const uint8_t* d_data,
                                 const unsigned long long* offsets, const uint32_t* substream_bytes, int32_t n_substreams, hop_cu_part* parts, int32_t* levels, hop_sao_param* sao,
-                                size_t front, hop_parse_where* where) {
+                                size_t front, hop_parse_where* where, const int32_t* pic_qp) {
   if (!c || !p || (!data && !d_data) || (offsets && !d_data) || !substream_bytes || !parts) return hop_set_err(c, HOP_ERR_ARG, "hop_slice_data_parse: bad argument");
   if (c->shard_world > 1) return hop_set_err(c, HOP_ERR_ARG, "hop_slice_data_parse: a sharded context parses no slice data");
   if (c->bd_y != c->bd_c) return hop_set_err(c, HOP_ERR_ARG, "hop_slice_data_parse: luma and chroma bit depths differ");
@@ -141,8 +144,8 @@ extern "C" __attribute__((visibility("hidden"))) int hop_parse_device_at(hop_ctx
   char err[256]; size_t total = 0;
   int r = hop_parse_check(c->pic_w, ph, c->bd_y, n_pic, p, data ? data : d_data, substream_bytes, n_substreams, parts, sao, &total, err, sizeof(err));
   if (r) return hop_set_err(c, r, "%s", err);
-  uint8_t init[EN_STATES];
-  if (hop_ent_init_states(init, p->slice_type, p->qp)) return hop_set_err(c, HOP_ERR_ARG, "hop_slice_data_parse: slice type %d", p->slice_type);
+  std::vector<uint8_t> init; std::vector<int32_t> init_of;
+  if (hop_ent_init_tables(p->slice_type, p->qp, pic_qp, n_pic, init, init_of)) return hop_set_err(c, HOP_ERR_ARG, "hop_slice_data_parse: slice type %d, or a picture's qp outside 0..51", p->slice_type);
   const int wctu = (c->pic_w + 63) / 64, hctu = (ph + 63) / 64, n = wctu * hctu;
   const int n_sub = n_substreams, n_blocks = n_pic * n_sub;
   std::vector<unsigned long long> offs((size_t)n_blocks);
@@ -150,8 +153,8 @@ extern "C" __attribute__((visibility("hidden"))) int hop_parse_device_at(hop_ctx
   const bool dev_levels = levels != nullptr || where != nullptr;
   const size_t units = (size_t)n * n_pic * 256, parts_bytes = sizeof(hop_cu_part) * units, level_bytes = dev_levels ? sizeof(int32_t) * 6144 * (size_t)n * n_pic : 0,
                sao_bytes = sao ? sizeof(hop_sao_param) * 3 * (size_t)n * n_pic : 0;
-  const ParLayout L = par_layout(front, n_pic, n, hctu, n_blocks, dev_levels, sao != nullptr, d_data ? 0 : total + 256);
-  const size_t o_parts = L.o_parts, o_levels = L.o_levels, o_sao = L.o_sao, o_init = L.o_init, o_entry = L.o_entry, o_offs = L.o_offs, o_sizes = L.o_sizes, o_state = L.o_state,
+  const ParLayout L = par_layout(front, n_pic, n, hctu, n_blocks, dev_levels, sao != nullptr, d_data ? 0 : total + 256, (int)(init.size() / EN_STATES));
+  const size_t o_parts = L.o_parts, o_levels = L.o_levels, o_sao = L.o_sao, o_init = L.o_init, o_init_of = L.o_init_of, o_entry = L.o_entry, o_offs = L.o_offs, o_sizes = L.o_sizes, o_state = L.o_state,
                o_data = L.o_data;
   if (d_data && (!c->scratch || L.end > c->scratch_bytes)) return hop_set_err(c, HOP_ERR_STATE, "hop_slice_data_parse: the caller's scratch area of %zu bytes does not hold %zu", c->scratch_bytes, L.end);
   void* buf; r = hop_scratch(c, L.end, &buf); if (r) return r;
@@ -163,7 +166,8 @@ extern "C" __attribute__((visibility("hidden"))) int hop_parse_device_at(hop_ctx
   }
   HIPCHK(c, hipSetDevice(c->device));
   if (!d_data) HIPCHK(c, hipMemcpyAsync(b + o_data, data, total, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(b + o_init, init, EN_STATES, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(b + o_init, init.data(), init.size(), hipMemcpyHostToDevice, c->stream));
+  if (!init_of.empty()) HIPCHK(c, hipMemcpyAsync(b + o_init_of, init_of.data(), sizeof(int32_t) * init_of.size(), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(b + o_offs, offs.data(), sizeof(unsigned long long) * n_blocks, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(b + o_sizes, substream_bytes, sizeof(uint32_t) * n_blocks, hipMemcpyHostToDevice, c->stream));
   if (dev_levels) HIPCHK(c, hipMemsetAsync(b + o_levels, 0, level_bytes, c->stream));   // lane 0 stores the non-zero levels only
@@ -178,7 +182,7 @@ extern "C" __attribute__((visibility("hidden"))) int hop_parse_device_at(hop_ctx
   A.pic.e.parts = A.pic.parts; A.pic.e.levels = A.pic.levels; A.pic.e.sao = A.pic.sao; A.pic.e.scans = c->rdoq_scans;
   A.pic.wpp = p->wpp; A.pic.sao_shift = c->bd_y - std::min(c->bd_y, 10); A.pic.mi_size = p->mi_size; A.pic.mi_merge = !p->plain_intra;
   A.n_pic = n_pic; A.n_sub = n_sub;
-  A.init = (const uint8_t*)(b + o_init); A.entry = (uint8_t*)(b + o_entry);
+  A.init = (const uint8_t*)(b + o_init); A.init_of = init_of.empty() ? nullptr : (const int32_t*)(b + o_init_of); A.entry = (uint8_t*)(b + o_entry);
   A.data = d_data ? d_data : (const uint8_t*)(b + o_data); A.offs = (const unsigned long long*)(b + o_offs); A.sizes = (const uint32_t*)(b + o_sizes);
   A.state = (ParState*)(b + o_state);
   hipLaunchKernelGGL(k_parse_init, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, c->stream, A.pic.parts, units);

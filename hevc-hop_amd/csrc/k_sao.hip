@@ -154,24 +154,34 @@ extern "C" int hop_sao_apply(hop_ctx* c, const hop_sao_param* recon) {
   return HOP_OK;
 }
 
-extern "C" int hop_sao_frame(hop_ctx* c, const hop_sao_params* p, hop_sao_param* coded) {
-  if (!c || !p || !coded) return hop_set_err(c, HOP_ERR_ARG, "hop_sao_frame: bad argument");
-  SaoGeo g; int n_pic; int rc = sao_geo(c, g, n_pic, "hop_sao_frame"); if (rc != HOP_OK) return rc;
+// hop_sao_frame (every picture under p[0]: each == 0) and hop_sao_frame_pictures (picture k under p[k]: each == 1)
+static int sao_frame(hop_ctx* c, const hop_sao_params* p, int each, hop_sao_param* coded, const char* who) {
+  if (!c || !p || !coded) return hop_set_err(c, HOP_ERR_ARG, "%s: bad argument", who);
+  SaoGeo g; int n_pic; int rc = sao_geo(c, g, n_pic, who); if (rc != HOP_OK) return rc;
+  if (!each && hop_picture_qps(c))
+    return hop_set_err(c, HOP_ERR_ARG, "hop_sao_frame: the context holds a table of per-picture QPs (hop_ctx_set_picture_qps): one lambda does not decide pictures of different QPs, call hop_sao_frame_pictures with one hop_sao_params per picture");
+  if (each) for (int k = 1; k < n_pic; k++) {                             // one slice-data call writes the flags and the slice type of all pictures
+    for (int comp = 0; comp < 3; comp++) if (!p[k].enabled[comp] != !p[0].enabled[comp])
+      return hop_set_err(c, HOP_ERR_ARG, "%s: picture %d: enabled[%d] is %d, picture 0 has %d (one slice-data call writes the flags of all pictures)", who, k, comp, p[k].enabled[comp], p[0].enabled[comp]);
+    if (p[k].slice_type != p[0].slice_type) return hop_set_err(c, HOP_ERR_ARG, "%s: picture %d: slice_type is %d, picture 0 has %d", who, k, p[k].slice_type, p[0].slice_type);
+  }
   const size_t per_pic = (size_t)g.n_ctu * 3;
   int32_t* stats = (int32_t*)malloc((size_t)n_pic * per_pic * 5 * 32 * 2 * sizeof(int32_t));
   hop_sao_param* recon = (hop_sao_param*)malloc((size_t)n_pic * per_pic * sizeof(hop_sao_param));
-  if (!stats || !recon) { free(stats); free(recon); return hop_set_err(c, HOP_ERR_DEVICE, "hop_sao_frame: out of host memory"); }
+  if (!stats || !recon) { free(stats); free(recon); return hop_set_err(c, HOP_ERR_DEVICE, "%s: out of host memory", who); }
   rc = hop_sao_stats(c, stats);
   for (int k = 0; k < n_pic && rc == HOP_OK; k++) {                       // every picture of a stack is decided as a picture of its own
-    hop_sao_params pk = *p;                                               // a stack coded by hop_encode_frame on this context: every picture starts from the fraction ITS last CTU left
+    hop_sao_params pk = p[each ? k : 0];                                  // a stack coded by hop_encode_frame on this context: every picture starts from the fraction ITS last CTU left
     if (n_pic > 1 && c->rd_fraction && c->rd_fraction_n == n_pic * g.n_ctu) pk.rd_fraction = c->rd_fraction[(size_t)k * g.n_ctu + g.n_ctu - 1];
     rc = hop_sao_decide(g.n_ctu, g.wctu, g.bd, stats + (size_t)k * per_pic * 5 * 32 * 2, &pk, coded + (size_t)k * per_pic, recon + (size_t)k * per_pic);
-    if (rc != HOP_OK) hop_set_err(c, rc, "hop_sao_frame: hop_sao_decide refused its arguments");
+    if (rc != HOP_OK) hop_set_err(c, rc, "%s: hop_sao_decide refused its arguments", who);
   }
   if (rc == HOP_OK) rc = hop_sao_apply(c, recon);
   free(stats); free(recon);
   return rc;
 }
+extern "C" int hop_sao_frame(hop_ctx* c, const hop_sao_params* p, hop_sao_param* coded) { return sao_frame(c, p, 0, coded, "hop_sao_frame"); }
+extern "C" int hop_sao_frame_pictures(hop_ctx* c, const hop_sao_params* p, hop_sao_param* coded) { return sao_frame(c, p, 1, coded, "hop_sao_frame_pictures"); }
 
 // ---- PSNR: the sums of squared differences between the resident original and the reconstruction ----
 // replaces: the three loops of TEncGOP::xCalculateAddPSNR (TLibEncoder/TEncGOP.cpp:2383-2456).  One pass over both pictures (4 B per sample), a wave-level reduction and

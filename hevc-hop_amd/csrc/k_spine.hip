@@ -621,7 +621,13 @@ int hop_encode_frame(hop_ctx* c, const hop_enc_params* p, double* ctu_cost, uint
   }
   std::vector<int> g_off(G + 1, 0); for (int g = 0; g < G; g++) g_off[g + 1] = g_off[g] + n_pic / G + (g < n_pic % G ? 1 : 0);
   std::vector<hopspine::Encoder*> encs;
-  for (int k = 0, g = 0; k < n_pic; k++) { while (k >= g_off[g + 1]) g++; cfg.y_origin = k * c->sub_pitch; encs.push_back(new hopspine::Encoder(cfg, G > 1 ? (hopspine::Backend*)gbe[g] : (hopspine::Backend*)use)); }
+  const int32_t* pic_qp = hop_picture_qps(c);                             // hop_ctx_set_picture_qps: picture k is coded at its own QP -- quantiser, lambdas and initial coder all follow from its EncConfig
+  for (int k = 0, g = 0; k < n_pic; k++) {
+    while (k >= g_off[g + 1]) g++;
+    cfg.y_origin = k * c->sub_pitch;
+    if (pic_qp) { cfg.qp = pic_qp[k]; hopspine::finish_config(cfg); }     // (default_*_config is finish_config over its qp argument: everything QP-dependent is derived there)
+    encs.push_back(new hopspine::Encoder(cfg, G > 1 ? (hopspine::Backend*)gbe[g] : (hopspine::Backend*)use));
+  }
   hopspine::Encoder& enc = *encs[0];
   std::vector<FILE*> tfs;                                                  // candidate traces: trace_path, for the pictures of a stack trace_path.<k>
   if (p->trace_path && p->trace_path[0]) for (int k = 0; k < n_pic; k++) {

@@ -31,7 +31,8 @@
 
 extern "C" {
 int hop_ent_write_device(hop_ctx* c, const hop_slice_data_params* p, const hop_cu_part* parts, const int32_t* levels, const hop_sao_param* sao, uint8_t* out,
-                         size_t out_capacity, uint32_t* substream_bytes, int32_t* n_substreams, size_t reserve, const uint8_t** d_packed, uint8_t** d_reserve);   // k_entropy.hip
+                         size_t out_capacity, uint32_t* substream_bytes, int32_t* n_substreams, size_t reserve, const uint8_t** d_packed, uint8_t** d_reserve,
+                         const int32_t* pic_qp);                                                                                                              // k_entropy.hip
 int hop_strm_check(int pic_w, int pic_h, int bit_depth, const hop_stream_params* p, char* err, size_t errn);                                                  // host/hop_stream.cpp
 void hop_strm_parameter_sets(int pic_w, int pic_h, int bit_depth, const hop_stream_params* p, std::vector<uint8_t>& s);
 void hop_strm_slice_header(int pic_w, int pic_h, const hop_stream_params* p, const uint32_t* sub_bytes, const uint32_t* sub_emul, int n_sub, std::vector<uint8_t>& s);
@@ -39,12 +40,14 @@ void hop_strm_sei(int method, const uint8_t digest[3][16], std::vector<uint8_t>&
 void hop_strm_hash_plane(int method, int bit_depth, const int16_t* plane, int w, int h, size_t stride, uint8_t digest[16]);
 size_t hop_parse_work_bytes(const hop_ctx* c, size_t data_bytes, int n_substreams);                                                                         // k_parse.hip
 int hop_parse_device(hop_ctx* c, const hop_slice_data_params* p, const uint8_t* data, const uint8_t* d_data, const uint32_t* substream_bytes, int32_t n_substreams,
-                     hop_cu_part* parts, int32_t* levels, hop_sao_param* sao, size_t front);
+                     hop_cu_part* parts, int32_t* levels, hop_sao_param* sao, size_t front, const int32_t* pic_qp);
 struct hop_parse_where { const hop_cu_part* d_parts; const int32_t* d_levels; size_t end; };
 int hop_parse_device_at(hop_ctx* c, const char* who, const char* noun, const hop_slice_data_params* p, const uint8_t* data, const uint8_t* d_data, const unsigned long long* offsets,
-                        const uint32_t* substream_bytes, int32_t n_substreams, hop_cu_part* parts, int32_t* levels, hop_sao_param* sao, size_t front, hop_parse_where* where);
+                        const uint32_t* substream_bytes, int32_t n_substreams, hop_cu_part* parts, int32_t* levels, hop_sao_param* sao, size_t front, hop_parse_where* where,
+                        const int32_t* pic_qp);
 int hop_dec_device(hop_ctx* c, const char* who, const char* noun, const hop_dec_params* p, const hop_cu_part* parts, const int32_t* levels, const hop_cu_part* d_parts, const int32_t* d_levels,
-                   int32_t* d_order);                                                                                                                         // k_decode.hip
+                   int32_t* d_order, const int32_t* pic_qp);                                                                                                  // k_decode.hip
+int hop_dbk_device(hop_ctx* c, const hop_deblock_params* p, const hop_cu_part* parts, const int32_t* pic_qp);                                                 // k_deblock.hip
 }
 #include "../host/hop_stream_read.h"
 
@@ -547,7 +550,8 @@ extern "C" int hop_access_unit_write(hop_ctx* c, const hop_stream_params* p, con
   std::vector<uint32_t> sub(n_seg);
   int32_t got = -1;
   const uint8_t* d_packed = nullptr; uint8_t* d_res = nullptr;
-  r = hop_ent_write_device(c, &p->slice, parts, levels, sao, nullptr, sd_cap, sub.data(), &got, end, &d_packed, &d_res);
+  const int32_t* pic_qp = hop_picture_qps(c);                             // hop_ctx_set_picture_qps: picture k's slice data and slice_qp_delta at its own QP; the parameter sets carry none
+  r = hop_ent_write_device(c, &p->slice, parts, levels, sao, nullptr, sd_cap, sub.data(), &got, end, &d_packed, &d_res, pic_qp);
   if (r == HOP_ERR_ARG && got >= 0 && (size_t)got > sd_cap) {
     // the slice data alone outgrows the capacity: the size needed comes from a run into a buffer of our own that holds it
     size_t sd = 0; for (int i = 0; i < n_seg; i++) sd += sub[i];
@@ -586,7 +590,9 @@ extern "C" int hop_access_unit_write(hop_ctx* c, const hop_stream_params* p, con
   uint32_t max_chunks = 0; size_t out_at = 0, body_at = 0, rec_at = 0;
   for (int k = 0; k < n_pic; k++) {
     std::vector<uint8_t> h;
-    hop_strm_slice_header(c->pic_w, ph, p, &sub[(size_t)k * n_sub], &emul[(size_t)k * n_sub], n_sub, h);
+    hop_stream_params pk = *p;
+    if (pic_qp) pk.slice.qp = pic_qp[k];
+    hop_strm_slice_header(c->pic_w, ph, &pk, &sub[(size_t)k * n_sub], &emul[(size_t)k * n_sub], n_sub, h);
     if (h.size() > head_max) return hop_set_err(c, HOP_ERR_DEVICE, "hop_access_unit_write: slice header of %zu bytes", h.size());
     memcpy(&heads[(size_t)k * align256(head_max)], h.data(), h.size());
     size_t body = 0; for (int s = 0; s < n_sub; s++) body += sub[(size_t)k * n_sub + s];
@@ -783,12 +789,14 @@ extern "C" int hop_access_unit_decode(hop_ctx* c, const uint8_t* au, size_t au_b
   if (!parts) { own_parts.resize((size_t)n_ctu * 256); parts = own_parts.data(); }
   if (!levels) { own_levels.resize((size_t)n_ctu * 6144); levels = own_levels.data(); }
   if (sao_on && !sao_coded) { own_sao.resize((size_t)n_ctu * 3); sao_coded = own_sao.data(); }
-  r = hop_parse_device(c, &sl, nullptr, d_rbsp, sizes.data(), (int32_t)sizes.size(), parts, levels, sao_on ? sao_coded : nullptr, front);
+  // the stream's own QP all the way down: this entry does not read the context's table (hop_ctx_set_picture_qps).  (A stacked context is refused by hop_decode_frame below.)
+  const int32_t own_qp[1] = { sl.qp }; const int32_t* au_qp = (c->sub_pitch || c->sub_h) ? nullptr : own_qp;
+  r = hop_parse_device(c, &sl, nullptr, d_rbsp, sizes.data(), (int32_t)sizes.size(), parts, levels, sao_on ? sao_coded : nullptr, front, au_qp);
   if (r) return r;
   hop_dec_params dp; dp.qp = sl.qp; dp.cb_qp_offset = 0; dp.cr_qp_offset = 0; dp.plain_intra = sl.plain_intra; dp.schedule = 0;
   r = hop_decode_frame(c, &dp, parts, levels); if (r) return r;
   hop_deblock_params db; db.qp = sl.qp; db.beta_offset_div2 = 0; db.tc_offset_div2 = 0; db.cb_qp_offset = 0; db.cr_qp_offset = 0; db.disable = 0;
-  r = hop_deblock_frame(c, &db, parts); if (r) return r;
+  r = hop_dbk_device(c, &db, parts, au_qp); if (r) return r;
   if (sao_on) {
     std::vector<hop_sao_param> recon((size_t)n_ctu * 3);
     if (hop_sao_reconstruct_params(n_ctu, wctu, c->bd_y, sao_coded, recon.data())) return hop_set_err(c, HOP_ERR_ARG, "hop_access_unit_decode: the coded SAO parameters name a merge candidate that is not there");
@@ -812,11 +820,11 @@ extern "C" int hop_access_unit_decode(hop_ctx* c, const uint8_t* au, size_t au_b
 namespace {
 const char* strip_prefix(const char* s, const char* prefix) { const size_t n = strlen(prefix); return strncmp(s, prefix, n) ? s : s + n; }
 
-// the first field of the slice parameters in which b differs from a, or NULL
+// the first field of the slice parameters, the QP aside (every picture of a stack is parsed, decoded and deblocked at its own), in which b differs from a, or NULL
 const char* slice_params_differ(const hop_slice_data_params& a, const hop_slice_data_params& b, int* va, int* vb) {
-  const struct { const char* name; int32_t x, y; } f[7] = { { "qp", a.qp, b.qp }, { "slice_type", a.slice_type, b.slice_type }, { "wpp", a.wpp, b.wpp },
+  const struct { const char* name; int32_t x, y; } f[6] = { { "slice_type", a.slice_type, b.slice_type }, { "wpp", a.wpp, b.wpp },
     { "plain_intra", a.plain_intra, b.plain_intra }, { "sao_luma", a.sao_luma, b.sao_luma }, { "sao_chroma", a.sao_chroma, b.sao_chroma }, { "mi_size", a.mi_size, b.mi_size } };
-  for (int k = 0; k < 7; k++) if (f[k].x != f[k].y) { *va = f[k].x; *vb = f[k].y; return f[k].name; }
+  for (int k = 0; k < 6; k++) if (f[k].x != f[k].y) { *va = f[k].x; *vb = f[k].y; return f[k].name; }
   return nullptr;
 }
 }  // namespace
@@ -864,7 +872,7 @@ extern "C" int hop_access_units_decode(hop_ctx* c, const uint8_t* stream, const 
   const size_t o_in = seg(stream_bytes + ESC_LANE + 3), o_ends = seg(sizeof(uint32_t) * n_seg), o_cnt = seg(sizeof(uint32_t) * n_seg), o_chunks = seg(sizeof(uint32_t) * chunks_total),
                o_jobs = seg(sizeof(UneJob) * n_au), o_totals = seg(sizeof(unsigned long long) * n_au), o_viol = seg(sizeof(uint32_t) * n_au);
   for (int k = 0; k < n_au; k++) o_out[k] = seg(a[k].nal_len - (size_t)a[k].info.header_bytes + ESC_LANE);
-  const size_t front = align256(end), o_order = align256(front + hop_parse_work_bytes(c, 0, n_sub)), total = o_order + sizeof(int32_t) * n;
+  const size_t front = align256(end), o_order = align256(front + hop_parse_work_bytes(c, 0, n_sub)), total = o_order + sizeof(int32_t) * (n + 3 * (size_t)n_pic);   // (the CTU order and, behind it, the pictures' scaled QPs)
   void* buf; int r = hop_scratch(c, total, &buf); if (r) return r;
   char* b = (char*)buf;
   HIPCHK(c, hipSetDevice(c->device));
@@ -919,14 +927,16 @@ extern "C" int hop_access_units_decode(hop_ctx* c, const uint8_t* stream, const 
   if (!parts) { own_parts.resize(n * 256); parts = own_parts.data(); }
   if (sao_on && !sao_coded) { own_sao.resize(n * 3); sao_coded = own_sao.data(); }
   hop_parse_where where = { nullptr, nullptr, 0 };
-  r = hop_parse_device_at(c, who, "access unit", &sl, nullptr, (const uint8_t*)b, offs.data(), sizes.data(), n_sub, parts, levels, sao_on ? sao_coded : nullptr, front, &where);
+  std::vector<int32_t> au_qp(n_au);                                       // every access unit's own QP, handed down as an array: the context's table (hop_ctx_set_picture_qps) is neither read nor changed
+  for (int k = 0; k < n_au; k++) au_qp[k] = a[k].info.params.slice.qp;
+  r = hop_parse_device_at(c, who, "access unit", &sl, nullptr, (const uint8_t*)b, offs.data(), sizes.data(), n_sub, parts, levels, sao_on ? sao_coded : nullptr, front, &where, au_qp.data());
   if (r) return r;
   if (where.end > o_order || (char*)c->scratch != b) return hop_set_err(c, HOP_ERR_STATE, "%s: the parser's work area ends at %zu, %zu were kept for it", who, where.end, o_order);
   // 6. one decode over the parts and levels where the parser left them, one deblocking pass
   hop_dec_params dp; dp.qp = sl.qp; dp.cb_qp_offset = 0; dp.cr_qp_offset = 0; dp.plain_intra = sl.plain_intra; dp.schedule = 0;
-  r = hop_dec_device(c, who, "access unit", &dp, parts, nullptr, where.d_parts, where.d_levels, (int32_t*)(b + o_order)); if (r) return r;
+  r = hop_dec_device(c, who, "access unit", &dp, parts, nullptr, where.d_parts, where.d_levels, (int32_t*)(b + o_order), au_qp.data()); if (r) return r;
   hop_deblock_params db; db.qp = sl.qp; db.beta_offset_div2 = 0; db.tc_offset_div2 = 0; db.cb_qp_offset = 0; db.cr_qp_offset = 0; db.disable = 0;
-  r = hop_deblock_frame(c, &db, parts); if (r) return r;
+  r = hop_dbk_device(c, &db, parts, au_qp.data()); if (r) return r;
   // 7. the SAO parameters resolved per picture (a merge never leaves its picture), one apply
   if (sao_on) {
     std::vector<hop_sao_param> recon(n * 3);

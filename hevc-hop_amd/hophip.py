@@ -494,6 +494,30 @@ class Context:
         self._chk(self.L.hop_sao_frame(self.h, ctypes.byref(p), coded.ctypes.data), "hop_sao_frame")
         return coded
 
+    def sao_frame_pictures(self, params):
+        """hop_sao_frame_pictures: sao_frame with picture k decided under params[k] = (lambdas, slice_type, qp, rd_fraction[, enabled]) -- what the pictures of a stack coded
+        at different QPs (set_picture_qps) need; returns the coded parameters (n_ctu, 3) SAO_PARAM_DTYPE of the stack"""
+        assert len(params) == self.pictures, (len(params), self.pictures)
+        arr = (SaoParams * len(params))()
+        for k, q in enumerate(params):
+            lambdas, slice_type, qp, rd_fraction = q[:4]
+            enabled = q[4] if len(q) > 4 else (1, 1, 1)
+            arr[k] = SaoParams((ctypes.c_double * 3)(*lambdas), (ctypes.c_int32 * 3)(*enabled), slice_type, qp, rd_fraction)
+        coded = np.zeros((self._n_ctu(), 3), SAO_PARAM_DTYPE)
+        self.L.hop_sao_frame_pictures.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        self._chk(self.L.hop_sao_frame_pictures(self.h, arr, coded.ctypes.data), "hop_sao_frame_pictures")
+        return coded
+
+    def set_picture_qps(self, qps):
+        """hop_ctx_set_picture_qps (sticky): one QP per picture of the context; while set, encode_frame, deblock_frame, slice_data_write / parse, access_unit_write and
+        decode_stack give picture k the QP qps[k] and ignore their own qp argument.  None (or an empty list) clears the table; so does hop_ctx_set_stack."""
+        self.L.hop_ctx_set_picture_qps.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
+        if qps is None or len(qps) == 0:
+            self._chk(self.L.hop_ctx_set_picture_qps(self.h, 0, None), "hop_ctx_set_picture_qps")
+            return
+        a = np.ascontiguousarray(qps, np.int32)
+        self._chk(self.L.hop_ctx_set_picture_qps(self.h, len(a), a.ctypes.data), "hop_ctx_set_picture_qps")
+
     def sao_apply(self, recon):
         recon = np.ascontiguousarray(recon)
         assert recon.nbytes == self._n_ctu() * 3 * SAO_PARAM_DTYPE.itemsize

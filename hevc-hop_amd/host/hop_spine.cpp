@@ -1692,8 +1692,12 @@ void Encoder::wavefront_many(Encoder* const* encs, int n_pic, BatchInner* inner,
   const int lanes_per_pic = rif < rows ? rif : rows;
   if (lane_base < 0 || lane_base + (long)n_pic * lanes_per_pic > SPINE_LANES) throw 1;
   if (begin) { if (inner) inner->begin_frame(); else lanes[0]->begin_frame(); }
-  Coder init; memset(&init, 0, sizeof(init));
-  hop_cabac_init(&init.r, E0.cfg_.slice_type, E0.cfg_.qp); hop_cabac_cu_init(&init.c, E0.cfg_.slice_type, E0.cfg_.qp); hop_cabac_split_init(init.split, E0.cfg_.slice_type, E0.cfg_.qp);
+  std::vector<Coder> init((size_t)n_pic);                               // a picture's rows start from the models of its own slice QP (the pictures of a stack may differ in it)
+  for (int p = 0; p < n_pic; p++) {
+    const EncConfig& f = encs[p]->cfg_;
+    memset(&init[p], 0, sizeof(Coder));
+    hop_cabac_init(&init[p].r, f.slice_type, f.qp); hop_cabac_cu_init(&init[p].c, f.slice_type, f.qp); hop_cabac_split_init(init[p].split, f.slice_type, f.qp);
+  }
   for (int p = 0; p < n_pic; p++) {
     Encoder& E = *encs[p];
     for (size_t i = 0; i < E.pic.size(); i++) part_init(E.pic[i], 0);
@@ -1727,7 +1731,7 @@ void Encoder::wavefront_many(Encoder* const* encs, int n_pic, BatchInner* inner,
     for (int p = 0; p < n_pic; p++) for (int r = 0; r < rows; r++) {
       if (!ws.owned(r)) continue;
       pool.add([&, p, r]() {
-        code_row(*encs[p], p, r, lane_of(p, r), &pool, ws, init, [&](int st) { pool.wait_counter(&ws.steps_complete, st); }, cand[(size_t)p * rows + r]);
+        code_row(*encs[p], p, r, lane_of(p, r), &pool, ws, init[p], [&](int st) { pool.wait_counter(&ws.steps_complete, st); }, cand[(size_t)p * rows + r]);
       });
     }
     if (world > 1) pool.add([&]() { exchange_steps(E0, inner, pool, ws); });   // the exchange fiber
@@ -1739,7 +1743,7 @@ void Encoder::wavefront_many(Encoder* const* encs, int n_pic, BatchInner* inner,
     std::vector<std::thread> th;
     run_t0 = std::chrono::steady_clock::now();
     for (int p = 0; p < n_pic; p++) for (int r = 0; r < rows; r++) th.emplace_back([&, p, r]() {
-      try { code_row(*encs[p], p, r, lane_of(p, r), lanes[(p * rows + r) % n_lanes], ws, init, [&](int st) { ws.wait(st); }, cand[(size_t)p * rows + r]); }
+      try { code_row(*encs[p], p, r, lane_of(p, r), lanes[(p * rows + r) % n_lanes], ws, init[p], [&](int st) { ws.wait(st); }, cand[(size_t)p * rows + r]); }
       catch (...) {}                                                    // (code_row has recorded it in ws.error; rethrown below, after the join)
     });
     for (auto& t : th) t.join();

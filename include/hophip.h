@@ -130,6 +130,19 @@ int hop_set_fused_leaf(hop_ctx* ctx, int max_tus);
  * of all of them, each exactly as in a context of its own.  sub_h = sub_pitch = 0 returns to one picture. */
 int hop_stack_pitch(int sub_h);
 int hop_ctx_set_stack(hop_ctx* ctx, int sub_h, int sub_pitch);
+/* One QP per picture of the context (no counterpart in the reference, which codes the rate points of a frame in runs of their own, one -q each): the pictures of a
+ * stacked context coded, written, parsed and decoded side by side, each at a QP of its own -- the four rate points of one frame share a wavefront.  Sticky, like
+ * hop_encode_set_shard and hop_encode_set_exact.  n must be the context's picture count (1 on an unstacked context) and every qp[k] must lie in 0..51: anything else is
+ * HOP_ERR_ARG and the previous table stays.  n == 0 with qp == NULL clears the table; hop_ctx_set_stack clears it too, because the picture count changes.  The table is
+ * the parent's: a view (hop_ctx_create_view) cannot set one and sees its parent's, also one set after the view was made -- the picture groups of HOP_SPINE_GROUPS and the
+ * evaluation sets of hop_encode_frame are such views.
+ * While a table is set, every entry that applies one QP to all pictures gives picture k the value qp[k]: hop_encode_frame (quantiser, RDOQ / search / RD lambdas and the
+ * initial coder of picture k, exactly those of a context of its own at qp[k]), hop_deblock_frame (tc, beta and the chroma QP of an edge from its own picture),
+ * hop_slice_data_write and hop_slice_data_parse (the initial context models), hop_access_unit_write (also slice_qp_delta in picture k's slice header; the parameter sets
+ * carry no QP and do not change) and hop_decode_stack (the dequantiser).  The qp field of such an entry's params is still range-checked and is otherwise ignored.
+ * hop_sao_frame refuses while a table is set: hop_sao_frame_pictures takes the lambdas of every picture.  hop_decode_frame, hop_access_unit_decode and
+ * hop_access_units_decode neither read nor change the table: the last two take every picture's QP from its own stream.  With no table set nothing changes anywhere. */
+int hop_ctx_set_picture_qps(hop_ctx* ctx, int32_t n, const int32_t* qp);
 /* Raster-order visibility (no counterpart in the reference, which codes its CTUs in raster order and therefore never finds a coded sample below the CTU row it works in,
  * TEncSlice::compressSlice TEncSlice.cpp:1000-1196): while on, every read of the SS reference by hop_me_search (all stages), hop_pred_inter / hop_pred_cost and
  * hop_valid_pattern -- and their *_device forms -- returns the sentinel (-1) for a sample whose picture row lies at or below the bottom of the CTU row that holds the PU's
@@ -771,6 +784,11 @@ int hop_sao_apply(hop_ctx* ctx, const hop_sao_param* recon);
  * stacked context that hop_encode_frame coded on this context each start from the fraction their own last CTU left (params->rd_fraction is for a single picture).
  * replaces: TEncSampleAdaptiveOffset::SAOProcess (:251-283) after decidePicParams. */
 int hop_sao_frame(hop_ctx* ctx, const hop_sao_params* params, hop_sao_param* coded);
+/* hop_sao_frame with picture k of the context decided under params[k] (one per picture): its lambdas, its qp, and rd_fraction by the rule above -- what the pictures of a
+ * stack coded at different QPs (hop_ctx_set_picture_qps) need, since lambda follows the QP.  enabled (as flags) and slice_type must agree across the pictures, because
+ * one hop_slice_data_write call writes them for all: otherwise HOP_ERR_ARG, and the picture is untouched.  While a table of per-picture QPs is set, hop_sao_frame
+ * refuses with HOP_ERR_ARG and names this entry: it must not decide pictures of different QPs under one lambda. */
+int hop_sao_frame_pictures(hop_ctx* ctx, const hop_sao_params* params /* one per picture */, hop_sao_param* coded);
 
 /* replaces: the distortion loops and the PSNR formula of TEncGOP::xCalculateAddPSNR (TLibEncoder/TEncGOP.cpp:2383-2456) between the resident original and the context's
  * reconstruction picture (after hop_sao_frame: the final picture).  Per picture of the context and component (Y, Cb, Cr): ssd = the sum of squared differences, psnr in
@@ -1031,7 +1049,9 @@ int hop_access_unit_decode(hop_ctx* ctx, const uint8_t* au, size_t au_bytes, con
  * context's picture count, 1 on an unstacked one).  stream: the access units back to back, au_bytes[k] each.  They may be n pictures of one all-intra sequence (only the
  * first carries parameter sets) or n independent streams of one geometry and configuration.  Access unit k is read against the info of the nearest earlier access unit of
  * this call that carried parameter sets, or against `active` when there is none.  One parse serves all pictures: every access unit's params.slice must equal the first
- * one's in every field (HOP_ERR_ARG naming the access unit and the field); poc, parameter_sets, hash and nal_type may differ.
+ * one's in every field but qp (HOP_ERR_ARG naming the access unit and the field); qp, poc, parameter_sets, hash and nal_type may differ.  Every picture is parsed,
+ * decoded and deblocked at the QP of its own access unit -- four streams of one view at four QPs decode in one call -- and info[k] reports it.  The entry neither reads
+ * nor changes the table of hop_ctx_set_picture_qps: it passes its own per-picture array down.
  * In order: the host pass over every access unit's syntax, after which the scratch area is sized once; one upload of the stream and one set of unescape launches, the
  * access units side by side; one parse over the stack, every substream read where the unescape left it; parts, SAO parameters and parser states to the host (the plan
  * and the deblocking's checks need the parts); the levels stay where the parser wrote them for k_dec_ctu and are downloaded only when levels != NULL; one
