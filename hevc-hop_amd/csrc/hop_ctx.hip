@@ -361,6 +361,17 @@ int hop_ctx_set_picture_qps(hop_ctx* c, int32_t n, const int32_t* qp) {
   return HOP_OK;
 }
 
+// The quantiser of the leaf step (include/hophip.h).  The word lives in the parent's shared object beside the QP table: views read it through the pointer they copied, and
+// hop_make_pics hands it to every kernel that runs the leaf step (hop_pics::quant_mode).
+int hop_ctx_set_quant_mode(hop_ctx* c, const hop_quant_mode* m) {
+  if (!c || c->is_view || !c->pic_qps) return hop_set_err(c, HOP_ERR_ARG, "hop_ctx_set_quant_mode: bad argument (a view reads its parent's mode)");
+  if (!m) { c->pic_qps->quant_mode = 0; return HOP_OK; }
+  if ((m->rdoq != 0 && m->rdoq != 1) || (m->rdoq_ts != 0 && m->rdoq_ts != 1))
+    return hop_set_err(c, HOP_ERR_ARG, "hop_ctx_set_quant_mode: rdoq %d, rdoq_ts %d: each is 0 or 1", m->rdoq, m->rdoq_ts);
+  c->pic_qps->quant_mode = (m->rdoq ? 0 : HOP_QM_FLAT) | (m->rdoq_ts ? 0 : HOP_QM_FLAT_TS) | (m->i_slice ? HOP_QM_I_SLICE : 0);
+  return HOP_OK;
+}
+
 void hop_ctx_destroy(hop_ctx* c) {
   if (!c) return;
   if (c->stream) { (void)hipStreamSynchronize(c->stream); }

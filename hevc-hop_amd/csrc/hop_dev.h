@@ -68,7 +68,12 @@ struct hop_ctx : hop_lane {
   bool   levels_valid;               // coefpic holds the levels of the picture(s) the context holds: set by a hop_encode_frame that returned HOP_OK, cleared when one starts and by hop_decode_frame
   struct hop_pic_qps* pic_qps;       // hop_ctx_set_picture_qps: the table of per-picture QPs, the parent's own object (a view points at its parent's, so it sees every later change)
 };
-struct hop_pic_qps { int n; int32_t* qp; };   // n == 0: no table set
+struct hop_pic_qps { int n; int32_t* qp; int quant_mode; };   // n == 0: no table set; quant_mode: hop_ctx_set_quant_mode, kept in the same shared object for the same reason
+// hop_ctx_set_quant_mode as the kernels read it (hop_pics::quant_mode): a set bit switches something OFF the default, so the default mode { 1, 1, 0 } is the word 0
+#define HOP_QM_FLAT    1     // rdoq == 0: a unit without transform skip takes the plain quantiser
+#define HOP_QM_FLAT_TS 2     // rdoq_ts == 0: a transform-skip unit does
+#define HOP_QM_I_SLICE 4     // the plain quantiser's rounding offset is 171 (an I slice), not 85
+static inline int hop_quant_mode_word(const hop_ctx* c) { return c->pic_qps ? c->pic_qps->quant_mode : 0; }
 // the pictures of the context and the rows of one of them (hop_ctx_set_stack)
 static inline int hop_pictures(const hop_ctx* c, int* ph) {
   if (ph) *ph = c->sub_pitch ? c->sub_h : c->pic_h;
@@ -90,6 +95,7 @@ struct hop_pics {
   int16_t* pred_y; int16_t* pred_cb; int16_t* pred_cr;
   int pic_w, pic_h, stride_y, stride_c, bd_y, bd_c;
   int row_limit, sub_h, sub_pitch;   // hop_ctx_set_row_limit and the stack geometry it counts CTU rows in (hop_row_limit)
+  int quant_mode;                    // HOP_QM_*: hop_ctx_set_quant_mode (0: RDOQ everywhere, the default)
 };
 
 static inline hop_pics hop_make_pics(const hop_ctx* c) {
@@ -100,6 +106,7 @@ static inline hop_pics hop_make_pics(const hop_ctx* c) {
   p.pic_w = c->pic_w; p.pic_h = c->pic_h; p.stride_y = c->stride_y; p.stride_c = c->stride_c;
   p.bd_y = c->bd_y; p.bd_c = c->bd_c;
   p.row_limit = c->row_limit; p.sub_h = c->sub_h; p.sub_pitch = c->sub_pitch;
+  p.quant_mode = hop_quant_mode_word(c);
   return p;
 }
 

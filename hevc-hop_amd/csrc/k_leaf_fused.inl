@@ -7,6 +7,7 @@
 // tests/test_gpu_tq_intra.py runs both.
 #include "k_turd_dev.inl"
 #include "k_rdoq_dev.inl"
+#include "k_quant_flat_dev.inl"
 
 #define LEAF_WORK_PER_TU ((size_t)1024 * RQ_WORK_PER_COEF)           // the RDOQ work area of a 32x32 TU at ws = 1
 
@@ -18,7 +19,7 @@ struct LeafShared {
   // entropy table, and the RDOQ work area of TUs up to 16x16 (a 32x32 TU's 40 KB stay in HBM)
   int32_t src[1024], lev[1024], ebits[128]; hop_estbits eb; uint8_t ctx[152]; double work[256 * RQ_WORK_PER_COEF / 8];
   // the job records of the serial stages (also written to rq[j] / cb[j]) and what RDOQ's phases hand on
-  hop_rdoq_job rj; hop_coeff_bits_job bj; RqPhase ph; uint16_t cgMask[64];
+  hop_rdoq_job rj; hop_coeff_bits_job bj; union { RqPhase ph; QfPhase qf; }; uint16_t cgMask[64];      // (qf: a unit that does not use RDOQ, leaf_flat_*)
   // what RDOQ's preparation hands to the serial lane, in LDS for every size: |coefficient| * Q, the cost of coding nothing, the significance contexts (16 KB)
   int32_t plvl[1024]; double pcost[1024]; int32_t pctx[1024];
 };
@@ -63,6 +64,7 @@ __device__ static __forceinline__ void leaf_records(SH& L, const hop_tu_rd_job& 
   hop_rdoq_job rj; hop_coeff_bits_job bj;
   turd_records_make(jb, j, off, rj, bj);
   L.rj = rj; L.bj = bj; rq[j] = rj; cb[j] = bj;
+  L.qf.absSum = 0; L.qf.topSubset = -1;                               // (what leaf_flat_levels adds into.  Unconditional on purpose: under `if (flat)` k_inter_walk and k_iw_cand gain scratch and spills; a unit that uses RDOQ re-initialises these words, its RqPhase, in rdoq_prep_pos behind the barrier)
 }
 template <class SH>
 __device__ __noinline__ static void leaf_prepare(SH* Lg, const int lane, const int nlanes, double* wd) {
@@ -84,6 +86,29 @@ __device__ __noinline__ static void leaf_finish3(SH* Lg, const int lane, const i
   rdoq_finish_scatter(L.rj, L.scan, L.lev, as_j, wd, &L.ph, lane, nlanes);
 }
 
+// A unit that does not use RDOQ (hop_ctx_set_quant_mode; the rule of xQuant, TComTrQuant.cpp:1012: by its transform-skip flag): the plain quantiser and the reference's
+// sign-bit hiding of that branch (k_quant_flat_dev.inl) on all lanes, in the place of leaf_prepare ... leaf_finish3 and with no call on the serial lane.  No bit-estimate
+// table: only RDOQ reads one.  The remainders deltaU go where RDOQ's preparation would have gone (plvl / the work area).  Uniform over the lanes that serve the unit.
+__device__ static __forceinline__ bool leaf_is_flat(const hop_pics& pic, const hop_tu_rd_job& jb) { return (pic.quant_mode & ((jb.flags & HOP_TU_RD_TS) ? HOP_QM_FLAT_TS : HOP_QM_FLAT)) != 0; }
+__device__ static __forceinline__ int32_t* leaf_flat_du(LeafShared& L) { return L.plvl; }
+__device__ static __forceinline__ int32_t* leaf_flat_du(LeafSmallShared& L);
+template <class SH>
+__device__ static __forceinline__ QfUnit leaf_flat_unit(SH& L, const int i_slice) {
+  QfUnit u; u.log2_size = L.rj.log2_size; u.qp_scaled = L.rj.qp_scaled; u.bit_depth = L.rj.bit_depth; u.i_slice = i_slice; u.sign_hide = L.rj.sign_hide;
+  return u;
+}
+template <class SH>
+__device__ __noinline__ static void leaf_flat_levels(SH* Lg, const int lane, const int nlanes, const int i_slice) {
+  SH& L = *hopd_lds(Lg);
+  WS(HOP_WS_LEAF_RDOQ);
+  quant_flat_levels(leaf_flat_unit(L, i_slice), L.scan, L.src, L.lev, leaf_flat_du(L), &L.qf, lane, nlanes);
+}
+template <class SH>
+__device__ __noinline__ static void leaf_flat_sbh(SH* Lg, const int lane, const int nlanes, const int i_slice, uint32_t* as_j) {
+  SH& L = *hopd_lds(Lg);
+  quant_flat_sbh(leaf_flat_unit(L, i_slice), L.scan, L.src, L.lev, leaf_flat_du(L), as_j, &L.qf, lane, nlanes);
+}
+
 // one TU through all stages on the 256 threads of the calling workgroup (every thread calls; barriers inside)
 __device__ static void turd_fused_body(LeafShared& L_, const int j, const hop_tu_rd_job* jobs, int n, hop_pics pic, const hop_cabac_ctx* ctx_in, const int64_t* coef_off,
                                        const int32_t* entropy_bits, const uint16_t* scans, int32_t* coef, int32_t* levels, uint32_t* zs, uint32_t* ns, uint32_t* as,
@@ -93,6 +118,8 @@ __device__ static void turd_fused_body(LeafShared& L_, const int j, const hop_tu
   const hop_tu_rd_job jb = jobs[j];
   if (jb.log2_size < 2 || jb.log2_size > 5) return;                   // an empty slot of a job table (k_rqt.inl); uniform over the workgroup
   const bool small = jb.log2_size <= 3;
+  const bool flat = leaf_is_flat(pic, jb);                            // (mode and job: uniform over the workgroup)
+  const int i_slice = (pic.quant_mode & HOP_QM_I_SLICE) != 0;
   const int LOG2 = jb.log2_size, N2 = 1 << (2 * LOG2), CGN = N2 >> 4;
   WS(HOP_WS_LEAF_FORWARD);
   // residual, forward transform (or the transform-skip scaling), distortion of the zero block
@@ -111,17 +138,18 @@ __device__ static void turd_fused_body(LeafShared& L_, const int j, const hop_tu
   __syncthreads();
   // the serial stages: what depends on the position alone on all threads, the recurrences on thread 0
   double* const wd = LOG2 == 5 ? (double*)(work + (size_t)j * LEAF_WORK_PER_TU) : L.work;
-  leaf_prepare(&L, tid, 256, wd);
+  // (every barrier stands where all threads reach it, whichever quantiser the unit takes)
+  if (flat) leaf_flat_levels(&L, tid, 256, i_slice); else leaf_prepare(&L, tid, 256, wd);
   LEAF_SYNC();
-  leaf_groups(&L, tid, 256, wd);
+  if (flat) leaf_flat_sbh(&L, tid, 256, i_slice, as + j); else leaf_groups(&L, tid, 256, wd);
   LEAF_SYNC();
-  if (tid == 0) leaf_serial<LeafShared, 5>(&L, LOG2, wd);
+  if (!flat && tid == 0) leaf_serial<LeafShared, 5>(&L, LOG2, wd);
   LEAF_SYNC();                                                        // (RDOQ's three parts are one visit of LEAF_RDOQ on thread 0's timeline)
-  leaf_finish1(&L, tid, 256, wd);
+  if (!flat) leaf_finish1(&L, tid, 256, wd);
   LEAF_SYNC();
-  leaf_finish2(&L, tid, 256, wd);
+  if (!flat) leaf_finish2(&L, tid, 256, wd);
   LEAF_SYNC();
-  leaf_finish3(&L, tid, 256, as + j, wd);
+  if (!flat) leaf_finish3(&L, tid, 256, as + j, wd);
   LEAF_SYNC();
   WS(HOP_WS_LEAF_BITS);
   for (int i = tid; i < N2; i += 256) levels[off + i] = L.lev[i];     // (beside thread 0's count: both only read L.lev)
@@ -154,8 +182,9 @@ __global__ __launch_bounds__(256) void k_turd_fused(const hop_tu_rd_job* __restr
 // GPU holds at once.
 struct LeafSmallShared { TurdSmallShared t; CabacLds1 cab; uint16_t scan[64]; uint16_t scanCG[4]; double cgSig[4];
                          double work[64 * RQ_WORK_PER_COEF / 8]; hop_estbits eb; int32_t src[64], lev[64], ebits[128]; uint8_t ctx[152];   // everything the serial walk touches
-                         hop_rdoq_job rj; hop_coeff_bits_job bj; RqPhase ph; uint16_t cgMask[4]; };
+                         hop_rdoq_job rj; hop_coeff_bits_job bj; union { RqPhase ph; QfPhase qf; }; uint16_t cgMask[4]; };
 __device__ static __forceinline__ RqPrep leaf_prep_arrays(LeafSmallShared& L) { return rq_prep_in_work(L.work, 1 << (2 * L.rj.log2_size)); }
+__device__ static __forceinline__ int32_t* leaf_flat_du(LeafSmallShared& L) { return (int32_t*)L.work; }
 
 // The same body for the candidate walks (k_walk.inl): up to four small transform units of one tree node side by side, one per WAVE of the 256-thread workgroup, each with
 // its own LeafSmallShared; k_turd_fused_small is this body on a workgroup of one wave.  Every wave calls (the barriers are the workgroup's); a wave without a unit passes
@@ -169,6 +198,8 @@ __device__ static __forceinline__ void turd_fused_small_wave_body(LeafSmallShare
   if (j >= 0) jb = jobs[j];
   const bool live = j >= 0 && jb.log2_size >= 2 && jb.log2_size <= 3;      // (uniform over the wave)
   const int LOG2 = live ? jb.log2_size : 2, N2 = 1 << (2 * LOG2), CGN = N2 >> 4;
+  const bool flat = live && leaf_is_flat(pic, jb), rdoq = live && !flat;      // (uniform over the wave; the waves of a workgroup may differ: a unit beside its transform-skip twin)
+  const int i_slice = (pic.quant_mode & HOP_QM_I_SLICE) != 0;
   int64_t off = 0;
   WS(HOP_WS_LEAF_FORWARD);
   if (live) {
@@ -188,17 +219,17 @@ __device__ static __forceinline__ void turd_fused_small_wave_body(LeafSmallShare
   }
   __syncthreads();
   // the serial stages: what depends on the position alone on the wave's 64 lanes, the recurrences on its lane 0
-  if (live) leaf_prepare(&L, lane, 64, L.work);
+  if (flat) leaf_flat_levels(&L, lane, 64, i_slice); else if (rdoq) leaf_prepare(&L, lane, 64, L.work);
   LEAF_SYNC();
-  if (live) leaf_groups(&L, lane, 64, L.work);
+  if (flat) leaf_flat_sbh(&L, lane, 64, i_slice, as + j); else if (rdoq) leaf_groups(&L, lane, 64, L.work);
   LEAF_SYNC();
-  if (live && lane == 0) leaf_serial<LeafSmallShared, 3>(&L, LOG2, L.work);
+  if (rdoq && lane == 0) leaf_serial<LeafSmallShared, 3>(&L, LOG2, L.work);
   LEAF_SYNC();                                                          // (thread 0 waits here for the other waves' serial lanes: part of its one visit of LEAF_RDOQ)
-  if (live) leaf_finish1(&L, lane, 64, L.work);
+  if (rdoq) leaf_finish1(&L, lane, 64, L.work);
   LEAF_SYNC();
-  if (live) leaf_finish2(&L, lane, 64, L.work);
+  if (rdoq) leaf_finish2(&L, lane, 64, L.work);
   LEAF_SYNC();
-  if (live) leaf_finish3(&L, lane, 64, as + j, L.work);
+  if (rdoq) leaf_finish3(&L, lane, 64, as + j, L.work);
   LEAF_SYNC();
   WS_IF(live, HOP_WS_LEAF_BITS);
   if (live && lane < N2) levels[off + lane] = L.lev[lane];              // (beside lane 0's count: both only read L.lev)

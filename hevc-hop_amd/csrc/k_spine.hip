@@ -567,6 +567,11 @@ int hop_encode_frame(hop_ctx* c, const hop_enc_params* p, double* ctu_cost, uint
     if (p->wavefront_lag < 2) return hop_set_err(c, HOP_ERR_ARG, "hop_encode_frame: the exact wavefront (hop_encode_set_exact) needs wavefront_lag >= 2: a CTU's neighbour above and to the right must be coded");
     cfg.exact = 1;
   }
+  // the leaf step's quantiser (hop_ctx_set_quant_mode): the context's switches through the configuration, the rounding offset of the plain quantiser from the slice type
+  // of THIS call (plain_intra codes an I slice, the HOP configuration an ISS slice, which is not one) -- on the context for the length of the call, views included
+  { const int qm = hop_quant_mode_word(c); cfg.rdoq = !(qm & HOP_QM_FLAT); cfg.rdoq_ts = !(qm & HOP_QM_FLAT_TS); }
+  struct QuantMode { hop_ctx* c; int was; QuantMode(hop_ctx* c, const hopspine::EncConfig& g) : c(c), was(hop_quant_mode_word(c)) { if (c->pic_qps) c->pic_qps->quant_mode = (g.rdoq ? 0 : HOP_QM_FLAT) | (g.rdoq_ts ? 0 : HOP_QM_FLAT_TS) | (g.slice_type == 2 ? HOP_QM_I_SLICE : 0); }
+                     ~QuantMode() { if (c->pic_qps) c->pic_qps->quant_mode = was; } } quant_mode(c, cfg);
   struct RowLimit { hop_ctx* c; int was; RowLimit(hop_ctx* c, bool on) : c(c), was(c->row_limit) { if (on) c->row_limit = 1; } ~RowLimit() { c->row_limit = was; } } row_limit(c, exact);   // (views are made below and inherit it)
   {                                                                      // the images of the levels (one per candidate slot) and their part of the stash
     const size_t ctus = (size_t)((c->pic_w + 63) >> 6) * ((c->pic_h + 63) >> 6), want = ctus * (c->slots + 1) * COEF_PER_CTU * 4;

@@ -178,6 +178,43 @@ __global__ __launch_bounds__(256) void k_turd_inverse(const hop_tu_rd_job* __res
 __global__ __launch_bounds__(256) void k_turd_forward_small(const hop_tu_rd_job* __restrict__ jobs, int n, hop_pics pic, const int64_t* __restrict__ coef_off,                                                             int32_t* __restrict__ coef, uint32_t* __restrict__ zero_sse) { __shared__ TurdSmallShared sh; turd_forward_small_body(sh, threadIdx.x >> 6, threadIdx.x & 63, blockIdx.x * 4 + (threadIdx.x >> 6), jobs, n, pic, coef_off, coef, zero_sse); }
 __global__ __launch_bounds__(256) void k_turd_inverse_small(const hop_tu_rd_job* __restrict__ jobs, int n, hop_pics pic, const int64_t* __restrict__ coef_off,                                                             const int32_t* __restrict__ levels, const uint32_t* __restrict__ abs_sum, uint32_t* __restrict__ nz_sse,                                                             int16_t* __restrict__ rec_y, int16_t* __restrict__ rec_cb, int16_t* __restrict__ rec_cr) { __shared__ TurdSmallShared sh; turd_inverse_small_body(sh, threadIdx.x >> 6, threadIdx.x & 63, blockIdx.x * 4 + (threadIdx.x >> 6), jobs, n, pic, coef_off, levels, abs_sum, nz_sse, rec_y, rec_cb, rec_cr); }
 __global__ void k_turd_setup(const hop_tu_rd_job* __restrict__ jobs, int n, const hop_cabac_ctx* __restrict__ ctx_in, const int64_t* __restrict__ coef_off,                              const int32_t* __restrict__ entropy_bits, hop_estbits* __restrict__ tables, hop_rdoq_job* __restrict__ rq, hop_coeff_bits_job* __restrict__ cb) { turd_setup_body(blockIdx.x * blockDim.x + threadIdx.x, jobs, n, ctx_in, coef_off, entropy_bits, tables + (blockIdx.x * blockDim.x + threadIdx.x), rq, cb); }
+
+// ---- hop_ctx_set_quant_mode in the staged pipeline: the units that do not use RDOQ (the rule of xQuant, TComTrQuant.cpp:1012) ----
+#include "k_quant_flat_dev.inl"
+__device__ static inline bool turd_is_flat(const int quant_mode, const hop_tu_rd_job& jb) { return (quant_mode & ((jb.flags & HOP_TU_RD_TS) ? HOP_QM_FLAT_TS : HOP_QM_FLAT)) != 0; }
+// k_turd_setup for a batch in which some unit may be one: such a unit gets its records but no bit-estimate table (only RDOQ reads one), and its RDOQ record carries a size
+// of no class (0), so that k_rdoq_classify puts it on no list and k_rdoq leaves it alone
+__global__ void k_turd_setup_mode(const hop_tu_rd_job* __restrict__ jobs, int n, const hop_cabac_ctx* __restrict__ ctx_in, const int64_t* __restrict__ coef_off,
+                                  const int32_t* __restrict__ entropy_bits, hop_estbits* __restrict__ tables, hop_rdoq_job* __restrict__ rq, hop_coeff_bits_job* __restrict__ cb,
+                                  const int quant_mode) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const hop_tu_rd_job jb = jobs[i];
+  if (!turd_is_flat(quant_mode, jb)) { turd_setup_body(i, jobs, n, ctx_in, coef_off, entropy_bits, tables + i, rq, cb); return; }
+  hop_rdoq_job r; hop_coeff_bits_job b;
+  turd_records_make(jb, i, coef_off[i], r, b);
+  r.log2_size = 0;
+  rq[i] = r; cb[i] = b;
+}
+// their quantiser: a workgroup per unit, the two phases of k_quant_flat_dev.inl on its 256 threads; levels and remainders in LDS, the levels written out at the end.
+// A unit that uses RDOQ (or an empty slot) is left to k_rdoq: uniform over the workgroup, before any barrier.
+__global__ __launch_bounds__(256) void k_quant_flat(const hop_tu_rd_job* __restrict__ jobs, const int64_t* __restrict__ coef_off, const uint16_t* __restrict__ scans,
+                                                    const int32_t* __restrict__ coef, int32_t* __restrict__ levels, uint32_t* __restrict__ abs_sum, const int quant_mode) {
+  __shared__ int32_t s_lev[1024], s_du[1024]; __shared__ QfPhase s_ph;
+  const hop_tu_rd_job jb = jobs[blockIdx.x];
+  if (jb.log2_size < 2 || jb.log2_size > 5 || !turd_is_flat(quant_mode, jb)) return;
+  const int tid = threadIdx.x, N2 = 1 << (2 * jb.log2_size);
+  const int64_t off = coef_off[blockIdx.x];
+  const uint16_t* scan = scans + jb.scan_idx * 1360 + (jb.log2_size == 2 ? 0 : jb.log2_size == 3 ? 16 : jb.log2_size == 4 ? 80 : 336);
+  QfUnit u; u.log2_size = jb.log2_size; u.qp_scaled = jb.qp_scaled; u.bit_depth = jb.bit_depth; u.i_slice = (quant_mode & HOP_QM_I_SLICE) != 0; u.sign_hide = jb.sign_hide;
+  if (tid == 0) { s_ph.absSum = 0; s_ph.topSubset = -1; }
+  __syncthreads();
+  quant_flat_levels(u, scan, coef + off, s_lev, s_du, &s_ph, tid, 256);
+  __syncthreads();
+  quant_flat_sbh(u, scan, coef + off, s_lev, s_du, abs_sum + blockIdx.x, &s_ph, tid, 256);
+  __syncthreads();
+  for (int i = tid; i < N2; i += 256) levels[off + i] = s_lev[i];
+}
 __global__ void k_turd_decide(const hop_tu_rd_job* __restrict__ jobs, int n, const hop_cabac_ctx* __restrict__ ctx_in, const int64_t* __restrict__ coef_off,                               const int32_t* __restrict__ entropy_bits, const uint32_t* __restrict__ abs_sum, const unsigned long long* __restrict__ frac,                               const uint32_t* __restrict__ zero_sse, const uint32_t* __restrict__ nz_sse, int32_t* __restrict__ levels,                               hop_tu_rd_result* __restrict__ res) { turd_decide_body(blockIdx.x * blockDim.x + threadIdx.x, jobs, n, ctx_in, coef_off, entropy_bits, abs_sum, frac, zero_sse, nz_sse, levels, res); }
 
 // size_hint: 0 = transform sizes unknown / mixed, 1 = every TU is 4x4 or 8x8 (one wave per TU), 2 = every TU is 16x16 or 32x32
@@ -199,9 +236,14 @@ int hop_launch_tu_rd(hop_ctx* c, int n, const hop_tu_rd_job* d_jobs, const hop_c
   const int pr = hop_prof_begin(c, HOP_K_TQ, (uint64_t)n);
   if (size_hint != 1) hipLaunchKernelGGL(k_turd_forward, dim3(n), dim3(256), 0, c->stream, d_jobs, pic, d_coef_off, coef, zs);
   if (size_hint != 2) hipLaunchKernelGGL(k_turd_forward_small, dim3((n + 3) / 4), dim3(256), 0, c->stream, d_jobs, n, pic, d_coef_off, coef, zs);
-  hipLaunchKernelGGL(k_turd_setup, dim3((n + 63) / 64), dim3(64), 0, c->stream, d_jobs, n, d_ctx, d_coef_off, hop_entropy_bits_device(c), tab, rq, cb);
+  const int qm = pic.quant_mode, any_flat = (qm & (HOP_QM_FLAT | HOP_QM_FLAT_TS)) != 0, all_flat = (qm & HOP_QM_FLAT) && (qm & HOP_QM_FLAT_TS);
+  if (!any_flat) hipLaunchKernelGGL(k_turd_setup, dim3((n + 63) / 64), dim3(64), 0, c->stream, d_jobs, n, d_ctx, d_coef_off, hop_entropy_bits_device(c), tab, rq, cb);
+  else {                                                               // hop_ctx_set_quant_mode: the units that do not use RDOQ take the plain quantiser
+    hipLaunchKernelGGL(k_turd_setup_mode, dim3((n + 63) / 64), dim3(64), 0, c->stream, d_jobs, n, d_ctx, d_coef_off, hop_entropy_bits_device(c), tab, rq, cb, qm);
+    hipLaunchKernelGGL(k_quant_flat, dim3(n), dim3(256), 0, c->stream, d_jobs, d_coef_off, c->rdoq_scans, coef, d_levels, as, qm);
+  }
   hop_prof_end(c, pr);
-  r = hop_launch_rdoq(c, n, rq, tab, coef, d_levels, as, b + o_wk); if (r) return r;
+  if (!all_flat) { r = hop_launch_rdoq(c, n, rq, tab, coef, d_levels, as, b + o_wk); if (r) return r; }
   r = hop_launch_coeff_bits(c, n, cb, d_ctx, d_levels, fr, nullptr); if (r) return r;
   const int pr2 = hop_prof_begin(c, HOP_K_TQ, 0);
   if (size_hint != 1) hipLaunchKernelGGL(k_turd_inverse, dim3(n), dim3(256), 0, c->stream, d_jobs, pic, d_coef_off, d_levels, as, ns, c->rec[0], c->rec[1], c->rec[2]);

@@ -119,6 +119,10 @@ class DeblockParams(ctypes.Structure):   # hop_deblock_params
                 ("disable", ctypes.c_int32)]
 
 
+class QuantMode(ctypes.Structure):       # hop_quant_mode
+    _fields_ = [("rdoq", ctypes.c_int32), ("rdoq_ts", ctypes.c_int32), ("i_slice", ctypes.c_int32)]
+
+
 class DecParams(ctypes.Structure):       # hop_dec_params
     _fields_ = [("qp", ctypes.c_int32), ("cb_qp_offset", ctypes.c_int32), ("cr_qp_offset", ctypes.c_int32), ("plain_intra", ctypes.c_int32), ("schedule", ctypes.c_int32)]
 
@@ -200,7 +204,7 @@ MIRRORS = {"hop_pu_job": PU_JOB_DTYPE, "hop_pu_result": PU_RESULT_DTYPE, "hop_pr
            "hop_rqt_result": RQT_RESULT_DTYPE, "hop_cu_syntax": CU_SYNTAX_DTYPE, "hop_intra_cu_syntax": INTRA_CU_SYNTAX_DTYPE, "hop_intra_rqt_opt": INTRA_RQT_OPT_DTYPE,
            "hop_intra_search_job": INTRA_SEARCH_JOB_DTYPE, "hop_intra_search_result": INTRA_SEARCH_RESULT_DTYPE, "hop_cu_part": CU_PART_DTYPE, "hop_enc_params": EncParams,
            "hop_deblock_params": DeblockParams, "hop_sao_param": SAO_PARAM_DTYPE, "hop_sao_params": SaoParams, "hop_dec_params": DecParams,
-           "hop_slice_data_params": SliceDataParams, "hop_stream_params": StreamParams, "hop_stream_info": StreamInfo, "hop_walk_stamps_total": WalkStampsTotal}
+           "hop_slice_data_params": SliceDataParams, "hop_stream_params": StreamParams, "hop_stream_info": StreamInfo, "hop_walk_stamps_total": WalkStampsTotal, "hop_quant_mode": QuantMode}
 
 
 def mirror_size(m):
@@ -517,6 +521,17 @@ class Context:
             return
         a = np.ascontiguousarray(qps, np.int32)
         self._chk(self.L.hop_ctx_set_picture_qps(self.h, len(a), a.ctypes.data), "hop_ctx_set_picture_qps")
+
+    def set_quant_mode(self, rdoq=1, rdoq_ts=1, i_slice=0):
+        """hop_ctx_set_quant_mode (sticky): a transform unit is quantised by RDOQ iff (its transform_skip_flag ? rdoq_ts : rdoq), otherwise by the reference's plain quantiser
+        (offset 171 with i_slice, else 85) and its sign-bit hiding.  set_quant_mode(None) passes NULL: back to the default {1, 1, 0}.  encode_frame takes i_slice from its
+        plain_intra, whatever was set here."""
+        self.L.hop_ctx_set_quant_mode.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        if rdoq is None:
+            self._chk(self.L.hop_ctx_set_quant_mode(self.h, None), "hop_ctx_set_quant_mode")
+            return
+        m = QuantMode(int(rdoq), int(rdoq_ts), int(i_slice))
+        self._chk(self.L.hop_ctx_set_quant_mode(self.h, ctypes.byref(m)), "hop_ctx_set_quant_mode")
 
     def sao_apply(self, recon):
         recon = np.ascontiguousarray(recon)
@@ -1182,3 +1197,18 @@ def sao_reconstruct_params(coded, ctus_per_row, bit_depth, lib=None):
     if r != 0:
         raise HopError("hop_sao_reconstruct_params: %d" % r)
     return recon
+
+
+def quant_flat_tu_host(coef, bit_depth=8, qp_scaled=32, i_slice=0, sign_hide=1, scan_idx=0, nlanes=256, descending=0, lib=None):
+    """hop_quant_flat_tu_host: the leaf step's quantiser for a unit that does not use RDOQ (csrc/k_quant_flat_dev.inl on the host) on one N x N block of coefficients, its
+    phases over `nlanes` emulated lanes; returns (levels (N, N) int32, abs_sum)"""
+    L = lib or load()
+    c = np.ascontiguousarray(coef, np.int32)
+    N = c.shape[0]
+    assert c.shape == (N, N) and N in (4, 8, 16, 32)
+    lev = np.zeros((N, N), np.int32); a = ctypes.c_uint32(0)
+    L.hop_quant_flat_tu_host.argtypes = [ctypes.c_int] * 6 + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
+    r = L.hop_quant_flat_tu_host(bit_depth, qp_scaled, i_slice, N.bit_length() - 1, sign_hide, scan_idx, c.ctypes.data, lev.ctypes.data, ctypes.byref(a), nlanes, descending)
+    if r != 0:
+        raise HopError("hop_quant_flat_tu_host: %d" % r)
+    return lev, int(a.value)

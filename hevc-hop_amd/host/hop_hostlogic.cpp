@@ -383,6 +383,7 @@ int hop_sizeof(const char* name) {
   S(hop_sao_param);
   S(hop_sao_params);
   S(hop_dec_params);
+  S(hop_quant_mode);
   S(hop_slice_data_params);
   S(hop_stream_params);
   S(hop_stream_info);

@@ -49,6 +49,7 @@ void default_hop_config(EncConfig& c, int pic_w, int pic_h, int qp, int mi_size)
   c.amp = 1; c.fen = 1; c.hadme = 1; c.fdm = 1; c.esd = 0; c.cfm = 0; c.ecu = 0;
   c.log2_max_tu = 5; c.log2_min_tu = 2; c.tu_max_depth_inter = 3; c.tu_max_depth_intra = 3;
   c.sign_hide = 1; c.use_ts = 1; c.ts_fast = 1; c.strong_intra = 1; c.wpp = 0;
+  c.rdoq = 1; c.rdoq_ts = 1;
   { const char* e = getenv("HOP_SPINE_FUSE_PRED"); c.fuse_pred = e ? atoi(e) != 0 : 1; }
   finish_config(c);
 }

@@ -49,6 +49,10 @@ struct EncConfig {
   // -- row r starts CTU c once row r - 1 has retired CTU min(c + lag - 1, columns - 1) -- instead of common steps, and a request that would read samples of the row above
   // at a column that row has not retired yet (a motion search's window, a validity probe) waits until it has.  The decisions are then the raster-order ones for any lag >= 2.
   int exact;
+  // The leaf step's quantiser (--RDOQ / --RDOQTS, hop_ctx_set_quant_mode; default 1, 1): a transform unit is quantised by RDOQ iff (transform skip ? rdoq_ts : rdoq),
+  // otherwise by the reference's plain quantiser, whose rounding offset follows slice_type (171 for an I slice).  Read by the device entry, which hands it to the
+  // kernels of its backend for the length of the call; no decision of the spine reads it.
+  int rdoq, rdoq_ts;
   // derived by finish_config()
   double lambda, sqrt_lambda, lambda_rdoq[3], dist_weight[2];
   uint32_t lambda_sad;

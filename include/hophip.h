@@ -143,6 +143,21 @@ int hop_ctx_set_stack(hop_ctx* ctx, int sub_h, int sub_pitch);
  * hop_sao_frame refuses while a table is set: hop_sao_frame_pictures takes the lambdas of every picture.  hop_decode_frame, hop_access_unit_decode and
  * hop_access_units_decode neither read nor change the table: the last two take every picture's QP from its own stream.  With no table set nothing changes anywhere. */
 int hop_ctx_set_picture_qps(hop_ctx* ctx, int32_t n, const int32_t* qp);
+/* The quantiser of the leaf step (the reference's --RDOQ / --RDOQTS switches, TEncCfg::m_useRDOQ / m_useRDOQTS): a transform unit is quantised by RDOQ iff
+ * (its transform_skip_flag ? rdoq_ts : rdoq), the rule of TComTrQuant::xQuant (TLibCommon/TComTrQuant.cpp:1012); otherwise by the plain branch (:1071-1116): the flat
+ * quantiser with the rounding offset 171/512 (i_slice) or 85/512 of a step, followed by TComTrQuant::signBitHidingHDQ (:868-990) where the unit's job has sign_hide, and
+ * the bit-estimate table (TEncSbac::estBit), which only RDOQ reads, is not built for it (TLibEncoder/TEncSearch.cpp:1096, :1284, :6902, :6922, :7236, :7326).  Counted
+ * bits, the inverse path and every decision are unchanged; the mode changes no syntax.  rdoq and rdoq_ts are 0 or 1 (anything else: HOP_ERR_ARG, the mode stays);
+ * i_slice != 0 selects the offset 171: the slice is an I slice (an ISS slice is NOT an I slice, see hop_tu_job.is_i_slice).  mode == NULL: back to the default
+ * { 1, 1, 0 }, with which nothing changes anywhere.
+ * Sticky, like hop_encode_set_exact, and a property of the context, not of a picture: the one-picture, stacked, per-picture-QP, exact and sharded forms all honour it.
+ * The mode is the parent's: a view (hop_ctx_create_view) cannot set it and reads its parent's, also one set after the view was made.
+ * Every entry that quantises through the leaf step follows it: hop_tu_rd, hop_rqt*, hop_intra_rqt*, hop_intra_luma_search*, hop_intra_chroma_search*,
+ * hop_inter_cu_device_classes, hop_intra_cu_device_classes (i_slice from the mode) and hop_encode_frame, which takes i_slice from its plain_intra for the length of the
+ * call, whatever the mode says -- on the shared mode itself, also when the call is made on a view: no other entry may quantise through the parent or another of its
+ * views while it runs, and the mode is as it was when it returns.  hop_rdoq, hop_tu_roundtrip and the *_host yardsticks do not read it. */
+typedef struct { int32_t rdoq, rdoq_ts, i_slice; } hop_quant_mode;
+int hop_ctx_set_quant_mode(hop_ctx* ctx, const hop_quant_mode* mode);   /* NULL: back to the default {1, 1, 0} */
 /* Raster-order visibility (no counterpart in the reference, which codes its CTUs in raster order and therefore never finds a coded sample below the CTU row it works in,
  * TEncSlice::compressSlice TEncSlice.cpp:1000-1196): while on, every read of the SS reference by hop_me_search (all stages), hop_pred_inter / hop_pred_cost and
  * hop_valid_pattern -- and their *_device forms -- returns the sentinel (-1) for a sample whose picture row lies at or below the bottom of the CTU row that holds the PU's
@@ -403,6 +418,12 @@ int hop_tu_rd_device(hop_ctx* ctx, int n, const hop_tu_rd_job* d_jobs, const hop
  * by side, in ascending or descending lane order (hop_estbits_fill_host: every one of the table's 976 bytes is written, nothing is cleared first).  Same bytes. */
 int hop_estbits_setup_host(const hop_tu_rd_job* job, const hop_cabac_ctx* ctx, hop_estbits* out);
 int hop_estbits_fill_host(const hop_tu_rd_job* job, const hop_cabac_ctx* ctx, hop_estbits* out, int nlanes, int descending);
+/* host only, a yardstick like hop_rdoq_tu_phased_host (csrc/k_quant_flat_dev.inl compiled for the host): the quantiser the leaf step runs for a unit that does not use
+ * RDOQ (hop_ctx_set_quant_mode) -- the plain branch of xQuant and, with sign_hide, signBitHidingHDQ along scan scan_idx (0 diagonal, 1 horizontal, 2 vertical) -- its two
+ * phases spread over `nlanes` (1..1024) emulated lanes run in ascending (descending = 0) or descending order.  coef / level: the unit's N x N coefficients and levels;
+ * *abs_sum: uiAcSum, the sum of the levels before clip and hiding.  Same bytes whatever nlanes and the order. */
+int hop_quant_flat_tu_host(int bit_depth, int qp_scaled, int i_slice, int log2_size, int sign_hide, int scan_idx, const int32_t* coef, int32_t* level, uint32_t* abs_sum,
+                           int nlanes, int descending);
 
 /* ---- the mode-decision half of the intra rough search (rest of row a7) ---- */
 /* replaces: the candidate selection of TEncSearch::estIntraPredQT (TLibEncoder/TEncSearch.cpp:2440-2493) on the 35 SATDs of hop_intra_rough: per mode
@@ -425,7 +446,7 @@ int hop_intra_modes_device(hop_ctx* ctx, int n, const hop_intra_modes_job* d_job
  * encodeResAndCalcRdInterCU calls it (:6700) for a batch of CUs: the full search over transform sizes -- per node Y/Cb/Cr through
  * transformNxN with RDOQ, counted bits, inverse path, cbf-zero decision, the 4x4 transform-skip retry, the node's own cost; the
  * four children on the coder state the previous one left; the subtree recounted in syntax order; the split decision.  The
- * residual is original - prediction picture of the context.  RDOQ and RDOQTS on, no lossless coding, flat scaling lists. */
+ * residual is original - prediction picture of the context.  RDOQ and RDOQTS on unless hop_ctx_set_quant_mode says otherwise, no lossless coding, flat scaling lists. */
 typedef struct {
   int32_t x, y, log2_cu;           /* CU position (luma) and size, 3..6 */
   int32_t qp_scaled[3];            /* what setQPforQuant hands to setQpParam for Y, Cb, Cr */
@@ -515,7 +536,7 @@ int hop_intra_cu_bits(hop_ctx* ctx, int n, const hop_rqt_job* jobs, const hop_in
  * prediction, residual, DST / DCT with RDOQ on the current coder state, inverse path, reconstruction written back into the picture, SSE), for 4x4 nodes also the
  * transform-skip variant (:1424-1523), the bits through xGetIntraBitsQT (:957-980), the four children, the recount and the split decision (:1576-1700).
  * jobs: CU position / size / QP / lambdas / transform-tree limits and ctx_index (into ctx_in and cu_ctx_in) of hop_rqt_job; syntax: the CU's syntax elements, with
- * (tr_depth, part) = the node the PU starts at (0, 0 for 2Nx2N; 1, k * parts / 4 for PU k of NxN); b_luma / b_chroma are not read.  RDOQ and RDOQTS on, RDpenalty 0,
+ * (tr_depth, part) = the node the PU starts at (0, 0 for 2Nx2N; 1, k * parts / 4 for PU k of NxN); b_luma / b_chroma are not read.  RDOQ and RDOQTS on unless hop_ctx_set_quant_mode says otherwise, RDpenalty 0,
  * no PCM / transquant bypass, not an I slice.  The reconstruction picture is read (neighbours) and written (the PU's blocks) as the search goes: the PUs of one call
  * must not lie in each other's neighbourhood (up to 2 * size to the right / below, one sample left / above); afterwards it holds the chosen tree's reconstruction. */
 typedef struct {

@@ -1,12 +1,13 @@
 #!/usr/bin/python3
-"""tools/walk_stamps.py [--out profiles/walk_stamps.json] | --show profiles/walk_stamps.json -- where thread 0 of a candidate walk's workgroup spends its cycles, stage by stage ("Stage stamps").
+"""tools/walk_stamps.py [--out profiles/walk_stamps.json] [--quant-mode RDOQ,RDOQTS] | --show profiles/walk_stamps.json -- where thread 0 of a candidate walk's workgroup spends its cycles, stage by stage ("Stage stamps").
 
 Runs in the DIAGNOSTIC build: HOP_LIB=hevc-hop_amd/libhophip_stamps.so (taken if HOP_LIB is unset; the product library refuses hop_walk_stamps_read).  The cases are
 tests/test_gpu_walk_codegen.py's (_case / _run, imported): inter 8x8 / 16x16 / 32x32, intra 8x8 NxN, intra 16x16, noisy content, n = 1 and n = 25 candidates of the class (the
 breadth of bench.py's batches); then one wavefront encode of the 448x192 --MIsize=15 picture of the stream tests, for the shares under a real mix of candidates.
 Per kernel and class it prints each stage's share of the workgroups' timelines and its cycles per visit.  The instrument's own cost is NOT subtracted: hop_walk_stamps_probe
 measures it (two stamps back to back; a whole stage boundary), and the column `stamp` says how much of a stage's cycles its boundaries can account for at that price.
-The numbers are shares of a fenced, slower build's timeline -- not run times of the product."""
+The numbers are shares of a fenced, slower build's timeline -- not run times of the product.
+--quant-mode 0,0 runs every context of the pass under hop_ctx_set_quant_mode { 0, 0 } (profiles/walk_stamps_rdoq0.json): what is left on the serial lane without RDOQ."""
 import argparse
 import datetime
 import importlib.util
@@ -78,7 +79,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "walk_stamps.json"))
     ap.add_argument("--show", metavar="JSON", help="print the tables of an earlier run's record and measure nothing")
+    ap.add_argument("--quant-mode", metavar="RDOQ,RDOQTS", help="hop_ctx_set_quant_mode for every context of the pass, e.g. 0,0")
     a = ap.parse_args()
+    if a.quant_mode:
+        mode = tuple(int(v) for v in a.quant_mode.split(","))
+        class ModeContext(hp.Context):
+            def __init__(self, *args, **kw):
+                super().__init__(*args, **kw)
+                self.set_quant_mode(mode[0], mode[1], 0)
+        hp.Context = ModeContext
     if a.show:
         with open(a.show) as f: report(json.load(f))
         return
@@ -88,7 +97,7 @@ def main():
     ctl = hp.Context(64, 64)
     names = hp.walk_stamps_stage_names(ctl.L)
     probe0 = ctl.walk_stamps_probe()
-    result = {"date": datetime.date.today().isoformat(), "library": os.path.basename(os.environ["HOP_LIB"]), "version": ctl.L.hop_version().decode(), "classes": [], "encode": None}
+    result = {"date": datetime.date.today().isoformat(), "library": os.path.basename(os.environ["HOP_LIB"]), "version": ctl.L.hop_version().decode(), "quant_mode": a.quant_mode or "1,1", "classes": [], "encode": None}
     for cls in CLASSES:
         for n in BREADTHS:
             wc._run(hp, cls, n, "noisy", {})                              # (once unmeasured: module load, first-touch of the work areas)
